@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the CRBM hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 without a launcher: this process starts the N ranks itself (plain child
 processes, created before anything here touches a GPU; RANK / LOCAL_RANK /
@@ -25,11 +25,18 @@ round 2 quoted the HIP-event time, which is still reported as
 Inputs (chain state, parameters) are resident in HBM when the timed region
 starts.
 
-With one GPU and `rocprofv3` on PATH the counters behind the roofline object
-(VALU issue cycles, HBM bytes) are collected for THIS box by three short child
-runs of tools/prof_gibbs.py under `rocprofv3 --pmc`, started before this process
-touches the GPU; otherwise the tracked values of profiles/gibbs_traffic.json
-are quoted and marked as not measured in this run.
+A plain run sets up, burns in and warms up the chains, times the K steps and
+prints the headline line.  `--dump-outputs DIR` then also writes the chain state
+the timed steps left (see dump_outputs) as DIR/<name>.npy.
+
+`--full` adds everything beside the headline: the roofline object and device-copy
+bandwidth, the training section (with the all-reduce when N > 1), the short runs
+of configs #4, #5, #1 and a generic model, and the CPU baseline.  With one GPU and
+`rocprofv3` on PATH the counters behind the roofline object (VALU issue cycles,
+HBM bytes) are collected for THIS box by three short child runs of
+tools/prof_gibbs.py under `rocprofv3 --pmc`, started before this process touches
+the GPU; otherwise the tracked values of profiles/gibbs_traffic.json are quoted
+and marked as not measured in this run.
 """
 import argparse
 import ctypes
@@ -58,6 +65,7 @@ CONFIGS = {
 TRAIN_WATCHDOG_S = 240
 SPAWN_TIMEOUT_S = 900
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec; the measured copy rate is reported next to it
+DUMP_BYTES = 48 << 20   # --dump-outputs writes at most this much (the chains of config #2 alone are 87 MB)
 
 
 def algorithmic_bytes_per_seq(K, M, L, ds):
@@ -85,6 +93,22 @@ def build_model(cfg, world, rank, device):
     model.motifs.set_value(W)
     model.rank, model.world_size = rank, world
     return model
+
+
+def dump_outputs(model, path):
+    """What a caller of the timed path receives: this rank's persistent chains after the last timed step, as
+    CRBM.get_fantasy() and get_fantasy_visible() return them (float32, exactly 0/1).  When the whole state exceeds
+    DUMP_BYTES, the same fixed, seeded sample of chains (sorted indices) is taken from every array."""
+    h, hp = model.get_fantasy()
+    arrays = {"fantasy_hidden": h, "fantasy_visible": model.get_fantasy_visible()}
+    if hp is not None:
+        arrays["fantasy_hidden_prime"] = hp
+    n = h.shape[0]
+    keep = min(n, max(1, DUMP_BYTES // sum(a[0].nbytes for a in arrays.values())))
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a[idx]))
 
 
 def cpu_share(hw_threads):
@@ -521,12 +545,22 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the chains after the last timed step (rank 0's) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (PMC counters, copy bandwidth), training "
+                         "section, other configurations, CPU baseline; --multi-step adds to it and needs it, the --no-* options "
+                         "leave parts of it out (a plain run leaves out all of them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="do not collect the chain kernel's PMC counters in child runs")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of configs #4, #5 and #1 behind the headline")
     ap.add_argument("--multi-step", action="store_true", help="also time 16 Gibbs steps per launch (informational)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.multi_step and not args.full:
+        ap.error("--multi-step reports into the roofline object, which only --full measures")
+    full = args.full
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
 
@@ -549,9 +583,9 @@ def main():
 
     # counters of the chain kernel on this box (children under rocprofv3, before this process touches the GPU)
     pmc, pmc_note = None, "not collected (multi-rank run, or --no-pmc)"
-    others = [c for c in ("cfg4", "cfg5") if world == 1 and args.config == "cfg2" and not args.no_other_configs]
+    others = [c for c in ("cfg4", "cfg5") if full and world == 1 and args.config == "cfg2" and not args.no_other_configs]
     other_pmc = {}
-    if world == 1 and not args.no_pmc and os.environ.get("CRBM_BENCH_PMC", "1") != "0":
+    if full and world == 1 and not args.no_pmc and os.environ.get("CRBM_BENCH_PMC", "1") != "0":
         try:
             pmc, pmc_note = measure_pmc(args.config)
         except Exception as e:                      # a report, never a reason to lose the line
@@ -576,7 +610,7 @@ def main():
         control.barrier()                 # ... and so are everybody else's
 
     copy_gbs = ctypes.c_float()
-    if os.environ.get("CRBM_BENCH_COPY_FIRST", "0") == "1":      # (A/B switch: the copy test in front of the timed region, as until round 3)
+    if full and os.environ.get("CRBM_BENCH_COPY_FIRST", "0") == "1":      # (A/B switch: the copy test in front of the timed region, as until round 3)
         model._call("crbm_copy_bandwidth", 1 << 30, 5, ctypes.byref(copy_gbs))
     # chains start at h = 0 (convRBM.py:168): 3000 burn-in steps (55 ms at config #2), then the W warm-up launches.
     # The burn-in is part of building the workload, not of the measurement: a persistent chain is never at
@@ -610,38 +644,38 @@ def main():
     model._call("crbm_time_gibbs", k, args.steps, ctypes.byref(total_ms))     # returns once its last launch has completed
     wall = time.perf_counter() - t0          # this rank's K steps, start barrier -> own stream idle; the closing barrier
     barrier()                                # (TCP round trips, a blocking read-back of the activity monitor) is not step time
-    clock_mhz = ctypes.c_float()
-    model._call("crbm_last_shader_clock", ctypes.byref(clock_mhz))     # sampled by the timed launches themselves
     wall, kernel_s = control.allreduce_max([wall, total_ms.value / 1e3])
     launches = args.steps
     steps_done = args.steps * k                  # Gibbs steps per rank in the timed region
     value = world * steps_done / wall            # host clock (barrier + synchronise on both sides), max over ranks
     value_device = world * steps_done / kernel_s
+    if args.dump_outputs and rank == 0:          # before anything below advances the chains
+        dump_outputs(model, args.dump_outputs)
 
-    # informational, opt-in (--multi-step): the same chain advanced 16 steps per launch (no
-    # per-launch fixed cost).  Off by default so that every crbm_gibbs launch of a default
-    # run is a one-step launch (the rocprofv3 per-kernel average then equals avg_launch_us).
-    us_per_step_k16 = None
-    if args.multi_step:
-        multi_ms = ctypes.c_float()
-        model._call("crbm_time_gibbs", 16, 5, ctypes.byref(multi_ms))
-        model._call("crbm_time_gibbs", 16, 40, ctypes.byref(multi_ms))
-        us_per_step_k16 = 1e3 * multi_ms.value / (40 * 16)
+    if full:
+        clock_mhz = ctypes.c_float()
+        model._call("crbm_last_shader_clock", ctypes.byref(clock_mhz))     # sampled by the timed launches themselves
 
-    # device-copy bandwidth of this GPU (the measured ceiling quoted beside the 8 TB/s spec) -- behind the timed region
-    if copy_gbs.value == 0.0:
-        model._call("crbm_copy_bandwidth", 1 << 30, 5, ctypes.byref(copy_gbs))
+        # informational, opt-in (--multi-step): the same chain advanced 16 steps per launch (no
+        # per-launch fixed cost).  Off by default so that every crbm_gibbs launch of a default
+        # run is a one-step launch (the rocprofv3 per-kernel average then equals avg_launch_us).
+        us_per_step_k16 = None
+        if args.multi_step:
+            multi_ms = ctypes.c_float()
+            model._call("crbm_time_gibbs", 16, 5, ctypes.byref(multi_ms))
+            model._call("crbm_time_gibbs", 16, 40, ctypes.byref(multi_ms))
+            us_per_step_k16 = 1e3 * multi_ms.value / (40 * 16)
 
-    # hidden-unit activity of the chain (workload descriptor, after timing)
-    hf, _ = model.get_fantasy()
-    activity = float(hf.mean())
+        # device-copy bandwidth of this GPU (the measured ceiling quoted beside the 8 TB/s spec) -- behind the timed region
+        if copy_gbs.value == 0.0:
+            model._call("crbm_copy_bandwidth", 1 << 30, 5, ctypes.byref(copy_gbs))
+
+        # hidden-unit activity of the chain (workload descriptor, after timing)
+        hf, _ = model.get_fantasy()
+        activity = float(hf.mean())
 
     out = None
     if rank == 0:
-        info = _lib.CrbmLaunchInfo()
-        lib.crbm_get_launch_info(h, ctypes.byref(info))
-        roof = roofline_object(args.config, cfg, info, kernel_s / launches, pmc, pmc_note, float(copy_gbs.value),
-                               int(lib.crbm_gibbs_state_bytes(h)), us_per_step_k16, clock_mhz=float(clock_mhz.value))
         out = {
             "metric": "Gibbs-steps/sec (PCD-1) at batch 8192x4x200, 10 motifs len 15" if args.config == "cfg2"
                       else "Gibbs-steps/sec, " + cfg["desc"],
@@ -656,16 +690,20 @@ def main():
             "config": {"workload": args.config + ": " + cfg["desc"], "chains_per_gpu": cfg["chains"],
                        "gibbs_steps_per_launch": k, "visible": "4x%d" % cfg["L"],
                        "hidden": "%dx%d" % (cfg["K"], cfg["L"] - cfg["M"] + 1),
-                       "parallelism": "chains sharded over %d GPU(s), no collective in the Gibbs step" % world,
-                       "hidden_activity": activity},
+                       "parallelism": "chains sharded over %d GPU(s), no collective in the Gibbs step" % world},
             "timing": "value and ms_per_step: host clock of each rank from the opening barrier (all streams idle) until its own K "
                       "launches have completed (event synchronise), max over ranks, closing barrier behind it (metric_version 3; version 2 = round 2 quoted the HIP-event time, now device_ms_per_step / "
                       "value_device; version 1 = round 1, host clock).  warmup_effective counts the chain burn-in launches "
                       "(chains start at h = 0) together with the --warmup launches",
             "chain_steps_per_s": value * cfg["chains"],
-            "roofline": roof,
-            "launch": launch_object(info),
         }
+        if full:
+            info = _lib.CrbmLaunchInfo()
+            lib.crbm_get_launch_info(h, ctypes.byref(info))
+            out["config"]["hidden_activity"] = activity
+            out["roofline"] = roofline_object(args.config, cfg, info, kernel_s / launches, pmc, pmc_note, float(copy_gbs.value),
+                                              int(lib.crbm_gibbs_state_bytes(h)), us_per_step_k16, clock_mhz=float(clock_mhz.value))
+            out["launch"] = launch_object(info)
 
     # The headline line is complete before the secondary section starts.  With N > 1 a
     # watchdog prints it anyway if the RCCL part of the training section should hang on
@@ -677,7 +715,8 @@ def main():
             return
         done["printed"] = True
         if rank == 0:
-            out["train"] = train_result
+            if full:
+                out["train"] = train_result
             if others:
                 # every BASELINE configuration that fits one GPU on the same clock (each in its own try: a report)
                 out["other_configs"] = {}
@@ -695,13 +734,13 @@ def main():
                     out["other_configs"]["generic_300x10"] = generic_model_timing()
                 except Exception as e:
                     out["other_configs"]["generic_300x10"] = {"error": str(e)[:300]}
-            if world == 1 and not args.no_cpu_baseline:
+            if full and world == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(cfg)
             print(json.dumps(out), flush=True)
 
     watchdog = None
     progress = {}
-    if world > 1 and not args.no_train:
+    if full and world > 1 and not args.no_train:
         def bail():
             # what the section had measured when it stopped making progress is kept (e.g. the RCCL steps when the
             # comparison run of the mapped-buffer all-reduce behind them hangs)
@@ -715,7 +754,7 @@ def main():
     # ---- secondary: full PCD-k training steps (with the RCCL all-reduce when N > 1) ----
     train = None
     failed = False
-    if not args.no_train:
+    if full and not args.no_train:
         try:
             rccl = world > 1 and not share_gpu
             n = cfg["chains"]
@@ -828,7 +867,7 @@ def main():
 
     if watchdog is not None:
         watchdog.cancel()
-    if rank == 0:
+    if rank == 0 and full:
         out["secondary_ok"] = not failed        # the training section is secondary: its failure is reported in the line
     emit(train)                                 # (train.error) and through the flag; the headline above stays valid
     control.close()

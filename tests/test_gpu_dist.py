@@ -161,7 +161,7 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     if not two:
         env["CRBM_BENCH_SHARE_GPU"] = "1"          # plumbing rehearsal on one GPU (no RCCL communicator: it refuses two ranks on one device)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3",
-                        "--no-cpu-baseline"], env=env, capture_output=True, timeout=600)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, timeout=600)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     import json
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])
@@ -174,3 +174,48 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     ipc = line["train"]["ipc_all_reduce"]
     assert "error" not in ipc and ipc["ok"] is True and ipc["replicas_identical"] is True and ipc["timed_out"] is False, ipc
     assert line["secondary_ok"] is True
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """`python bench.py --gpus 1` without --full prints the headline line and nothing measured beside it; with
+    --dump-outputs it writes the chain state of the last timed step: the same for the same arguments, another one
+    step later, and equal to the chains the same launches leave when run here (burn-in, warm-up, timed steps)."""
+    import ctypes
+    import json
+    import bench
+    lines = {}
+    for run, steps in (("a", 30), ("b", 30), ("c", 31)):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "5",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, timeout=300)
+        assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
+        lines[run] = json.loads(p.stdout.decode().strip().splitlines()[-1])
+    for run, line in lines.items():
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == (31 if run == "c" else 30) and line["warmup"] == 5
+        assert line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+        for key in ("roofline", "train", "other_configs", "cpu_baseline"):
+            assert key not in line, key
+    names = ["fantasy_hidden.npy", "fantasy_visible.npy"]
+    dumps = {}
+    for run in lines:
+        assert sorted(os.listdir(tmp_path / run)) == names
+        dumps[run] = [np.load(tmp_path / run / name) for name in names]
+        assert sum(os.path.getsize(tmp_path / run / name) for name in names) <= 64 << 20
+    for a, b, c in zip(dumps["a"], dumps["b"], dumps["c"]):
+        assert a.dtype == np.float32 and a.shape[0] > 1000 and np.isin(a, (0.0, 1.0)).all()
+        np.testing.assert_array_equal(a, b)
+        assert a.shape == c.shape and (a != c).any()                    # one more timed step moves the chains
+    assert (dumps["a"][1].sum(axis=2) == 1).all()                       # one letter per position
+    # the same launches in this process: bench.py's model, burn-in, warm-up and timed steps (one Gibbs step each)
+    line = lines["a"]
+    model = bench.build_model(bench.CONFIGS["cfg2"], 1, 0, 0)
+    ms = ctypes.c_float()
+    for launches in (line["chain_burn_in_launches"], line["warmup"], line["steps"]):
+        model._call("crbm_time_gibbs", 1, launches, ctypes.byref(ms))
+    h, _ = model.get_fantasy()
+    v = model.get_fantasy_visible()
+    idx = np.sort(np.random.default_rng(0).choice(h.shape[0], dumps["a"][0].shape[0], replace=False))
+    np.testing.assert_array_equal(dumps["a"][0], h[idx])
+    np.testing.assert_array_equal(dumps["a"][1], v[idx])

@@ -242,7 +242,7 @@ def test_load_state_defers_device_state(tmp_path):
 
 
 def test_bench_line_contract_of_the_tracked_profile():
-    """The bench line the round's evidence holds (profiles/r04_bench_cfg2.json, written by `python bench.py` on an
+    """The bench line the round's evidence holds (profiles/r04_bench_cfg2.json, written by `python bench.py --full` on an
     MI355X): the driver's keys, BASELINE.json's metric and config, a roofline object that names the resource that
     binds (no `bound: hbm`, no fraction above 1 posing as a utilisation) and is honest about partitioned launches
     (a step = launches_per_step overlapping launches; the step's time is not one launch's duration), the other

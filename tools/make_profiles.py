@@ -66,9 +66,12 @@ for cfg in ("cfg2", "cfg4", "cfg5"):
         parts = 1
         try:      # partitions of a chain launch at this config: the counters are per LAUNCH (one partition)
             line = json.loads(open(os.path.join(src, "bench_%s.json" % cfg)).read().strip().splitlines()[-1])
-            parts = int(line["launch"].get("chain_parts", 1))
         except Exception:
-            pass
+            line = None
+        if line is not None:
+            if "launch" not in line:
+                raise SystemExit("bench_%s.json has no launch object: it was written without bench.py --full" % cfg)
+            parts = int(line["launch"].get("chain_parts", 1))
         out[cfg] = {
             "counters": vals,
             "chain_parts": parts,

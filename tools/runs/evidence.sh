@@ -5,21 +5,22 @@ TAG=${1:-r03}
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $O
+R=$(pwd)   # the repository root (the profiled run below starts from another directory)
 export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest.log
-( time timeout -k 10 400 python bench.py ) > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "bench cfg2 rc=$?"
-( time timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench driver-style rc=$?"
-CRBM_BENCH_SHARE_GPU=1 timeout -k 10 300 python3 bench.py --gpus 6 --steps 20 --warmup 5 > $O/bench_6rank_one_gpu_rehearsal.json 2> $O/bench_6rank.err; echo "6-rank rehearsal rc=$?"
-CRBM_BENCH_SHARE_GPU=1 timeout -k 10 300 python3 bench.py --gpus 4 --config cfg5 --steps 20 --warmup 5 > $O/bench_cfg5_4rank_one_gpu_rehearsal.json 2> $O/bench_cfg5_4rank.err; echo "cfg5 4-rank rehearsal rc=$?"
+( time timeout -k 10 400 python bench.py --full ) > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "bench cfg2 rc=$?"
+( time timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench driver-style rc=$?"
+CRBM_BENCH_SHARE_GPU=1 timeout -k 10 300 python3 bench.py --gpus 6 --steps 20 --warmup 5 --full > $O/bench_6rank_one_gpu_rehearsal.json 2> $O/bench_6rank.err; echo "6-rank rehearsal rc=$?"
+CRBM_BENCH_SHARE_GPU=1 timeout -k 10 300 python3 bench.py --gpus 4 --config cfg5 --steps 20 --warmup 5 --full > $O/bench_cfg5_4rank_one_gpu_rehearsal.json 2> $O/bench_cfg5_4rank.err; echo "cfg5 4-rank rehearsal rc=$?"
 for cfg in cfg4 cfg5; do
-  timeout -k 10 300 python bench.py --config $cfg --steps 2000 --warmup 200 --no-cpu-baseline > $O/bench_${cfg}.json 2> $O/bench_${cfg}.err; echo "bench $cfg rc=$?"
+  timeout -k 10 300 python bench.py --config $cfg --steps 2000 --warmup 200 --full --no-cpu-baseline > $O/bench_${cfg}.json 2> $O/bench_${cfg}.err; echo "bench $cfg rc=$?"
 done
 KS=0,1,2,4,16 timeout -k 10 120 python tools/gibbs_k_scan.py cfg2 > $O/gibbs_steps_per_launch_scan.txt 2>&1
 # what a launch costs beyond its steps: the same scan with parts of the launch skipped (CRBM_GIBBS_DEBUG: 1 table copy,
 # 2 state load, 4 state store -- with 4 alone the chains stay at h = 0 and the top-down walk has nothing to do)
 for dbg in 0 1 2 6 7 4; do echo "== CRBM_GIBBS_DEBUG=$dbg"; CRBM_GIBBS_DEBUG=$dbg KS=0,1,2,16 timeout -k 10 120 python tools/gibbs_k_scan.py cfg2; done > $O/floor_scan.txt 2>&1
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-pmc > $O/bench_cfg2_under_rocprof.json 2> $O/bench_cfg2_under_rocprof.err; echo "prof rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 $R/bench.py --full --no-cpu-baseline --no-pmc > $O/bench_cfg2_under_rocprof.json 2> $O/bench_cfg2_under_rocprof.err; echo "prof rc=$?"
 A="SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_MFMA SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU"
 B="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_TRANS_F32"
 for cfg in cfg2 cfg4 cfg5; do

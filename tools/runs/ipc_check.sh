@@ -7,7 +7,7 @@ mkdir -p $O
 timeout -k 10 600 python -m pytest tests/test_gpu_dist.py -q > $O/ipc_pytest.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -3 $O/ipc_pytest.log
 [ $rc = 0 ] || exit $rc
 for n in 2 6; do
-  CRBM_BENCH_SHARE_GPU=1 timeout -k 10 300 python3 bench.py --gpus $n --steps 20 --warmup 5 > $O/ipc_bench_${n}rank.json 2> $O/ipc_bench_${n}rank.err; rc=$?; echo "$n-rank rehearsal rc=$rc"
+  CRBM_BENCH_SHARE_GPU=1 timeout -k 10 300 python3 bench.py --gpus $n --steps 20 --warmup 5 --full > $O/ipc_bench_${n}rank.json 2> $O/ipc_bench_${n}rank.err; rc=$?; echo "$n-rank rehearsal rc=$rc"
   [ $rc = 0 ] || exit $rc
 done
 python - <<PY

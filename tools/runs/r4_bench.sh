@@ -1,6 +1,6 @@
 # round 4: bench lines (driver style and default) after the partitioned launches
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r4_bench; mkdir -p $O
-( time timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench driver-style rc=$?"; tail -3 $O/bench_driver.err
+( time timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench driver-style rc=$?"; tail -3 $O/bench_driver.err
 python - <<PY
 import json
 d = json.loads(open("$O/bench_driver.json").read().strip().splitlines()[-1])
@@ -15,5 +15,5 @@ for c, o in d.get("other_configs", {}).items():
         print(c, o)
 print("cpu", d.get("cpu_baseline"))
 PY
-( time timeout -k 10 500 python3 bench.py --no-other-configs ) > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "bench default rc=$?"; cut -c1-400 $O/bench_cfg2.json
+( time timeout -k 10 500 python3 bench.py --full --no-other-configs ) > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "bench default rc=$?"; cut -c1-400 $O/bench_cfg2.json
 for n in 20 50 200; do echo "steps=$n: $(timeout -k 10 200 python3 bench.py --steps $n --warmup 5 --no-pmc --no-cpu-baseline --no-train --no-other-configs | cut -c1-330)"; done
