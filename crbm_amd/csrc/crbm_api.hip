@@ -283,6 +283,7 @@ int ensure_tables(crbm_handle* h) {
   const unsigned grid = (unsigned)std::max(1, std::min((h->ms.TABLES_ALL + 255) / 256, h->num_cu * 4));
   HIPCHK(jit_launch(h->jk.build_tables, t, grid, 1, 256, 0, h->stream));
   h->tables_dirty = false;
+  h->main_idle_hint = false;           // the main stream holds work now: partitions that fork next must wait for it
   return CRBM_OK;
 }
 
@@ -294,6 +295,7 @@ int ensure_solo_table(crbm_handle* h) {
   const unsigned grid = (unsigned)std::max(1, std::min((h->ms_solo.TAB + 255) / 256, h->num_cu * 4));
   HIPCHK(jit_launch(h->jk.build_gather_solo, t, grid, 1, 256, 0, h->stream));
   h->tf_solo_version = h->params_version;
+  h->main_idle_hint = false;
   return CRBM_OK;
 }
 
@@ -306,10 +308,12 @@ BigModel big_model(const crbm_handle* h) {
 }
 
 constexpr int SLAB_FALLBACK = -1000;     // slab_launch_stats / slab_launch_hgv: nothing launched, take the generic kernel
+// free energies of a generic DNA model slab by slab (slab_launch_fe), unless CRBM_SLAB_FE=0 or the slab's tables exceed the LDS
+bool slab_fe_on(const crbm_handle* h) { return h->slab && tab_bytes(h->slab) <= 160 * 1024 && env_int("CRBM_SLAB_FE", 1) != 0; }
 int slab_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int mode, unsigned long long* ones, uint32_t* masks,
                     uint32_t kind, uint32_t step, uint32_t seq_offset, hipStream_t st);
 int slab_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool data_half, hipStream_t st, ReduceArgs* reduce);
-int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe, float* fem, hipStream_t st);
+int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe, float* fem, DevBuf<float>* scratch, hipStream_t st);
 
 // h | v on packed rows: dense outputs (API), a count of sampled ones (evaluateData) or the masks of one strand (chain)
 int big_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int mode, float* act, float* prob, float* sample,
@@ -427,10 +431,11 @@ int big_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bo
 }
 
 // free energies (hits = 0) or motif-hit summaries (hits = 1) of n packed rows
+// (`fe_scratch`: the slab path's per-motif scratch, one per stream that may run this concurrently -- SweepSet::fe_scratch)
 int big_launch_eval(crbm_handle* h, const uint32_t* rows, int n, int L, int hits, float* fe, float* fem, float* hmax, float* hmean,
-                    unsigned long long* pos_fx, hipStream_t st) {
-  if (h->slab && !hits && env_int("CRBM_SLAB_FE", 1) != 0) {       // free energies: the specialised kernel, slab by slab
-    const int rc = slab_launch_fe(h, rows, n, L, fe, fem, st);
+                    unsigned long long* pos_fx, DevBuf<float>* fe_scratch, hipStream_t st) {
+  if (!hits && slab_fe_on(h)) {       // free energies: the specialised kernel, slab by slab
+    const int rc = slab_launch_fe(h, rows, n, L, fe, fem, fe_scratch, st);
     if (rc != SLAB_FALLBACK) return rc;
   }
   BigEvalArgs a;
@@ -939,25 +944,26 @@ int slab_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, b
 
 // Free energies of a generic DNA model (freeEnergy, evaluateData, the per-epoch evaluation of fit(): convRBM.py:657-697, :517-522):
 // the slab model's free-energy kernel leaves every slab's per-motif terms in a scratch (one launch, blockIdx.y = slab),
-// slab_fe_combine_kernel adds them up per sequence.
-int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe, float* fem, hipStream_t st) {
+// slab_fe_combine_kernel adds them up per sequence.  The scratch belongs to the caller's stream (the shadow handle's out_b
+// for the main stream, out_b2 for the second stream of a host-input sweep): the two streams' slabs run at the same time.
+int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe, float* fem, DevBuf<float>* scratch, hipStream_t st) {
   crbm_handle* s = h->slab;
   if (tab_bytes(s) > 160 * 1024) return SLAB_FALLBACK;
   int rc = slab_ensure_tables(h, st);
   if (rc) return rc;
   const size_t per_slab = (size_t)n * s->K;
-  HIPCHK(s->out_b.ensure(per_slab * h->slab_n));
+  HIPCHK(scratch->ensure(per_slab * h->slab_n));
   SlabFeArgs sa;
   sa.a.tables = h->d_slab_tables;
   sa.a.letters = rows;
   sa.a.n = n; sa.a.L = L; sa.a.Lh = L - h->M + 1; sa.a.LW = lw(h, L);
-  sa.a.fe = nullptr; sa.a.fem = s->out_b.p;
+  sa.a.fe = nullptr; sa.a.fem = scratch->p;
   sa.table_stride = s->ms.TABLES_ALL; sa.pad_ = 0;
   sa.fem_stride = (long long)per_slab;
   const unsigned gx = (unsigned)std::max(1, std::min((n + 3) / 4, h->num_cu * 8));
   HIPCHK(jit_launch(s->jk.slab_fe, sa, gx, (unsigned)h->slab_n, 256, (unsigned)tab_bytes(s), st));
   SlabFeCombineArgs ca;
-  ca.scratch = s->out_b.p;
+  ca.scratch = scratch->p;
   ca.c_log2e = h->d_slab_tables + s->ms.OFF_C;
   ca.letters = rows;
   ca.n = n; ca.L = L; ca.LW = lw(h, L);
@@ -1042,7 +1048,7 @@ int slab_setup(crbm_handle* h) {
 void slab_destroy(crbm_handle* h) {
   if (crbm_handle* s = h->slab) {
     if (s->d_sums) (void)hipFree(s->d_sums);
-    s->partials.release(); s->partials2.release(); s->out_b.release();
+    s->partials.release(); s->partials2.release(); s->out_b.release(); s->out_b2.release();
     if (s->jk.module) (void)hipModuleUnload(s->jk.module);
     delete s;
     h->slab = nullptr;
@@ -1707,6 +1713,9 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
   TRY(hipMalloc((void**)&hh->d_sums, (size_t)hh->sl.count * 4)); TRY(hipMemset(hh->d_sums, 0, (size_t)hh->sl.count * 4));
   TRY(hipMalloc((void**)&hh->d_ticket, 16)); TRY(hipMemset(hh->d_ticket, 0, 16));
   TRY(hipMalloc((void**)&hh->d_probe, 32)); TRY(hipMemset(hh->d_probe, 0, 32));
+  // the memsets above go out on the null stream, which the handle's non-blocking streams do not wait for: without this
+  // a zeroing of W, b, c could land after the crbm_set_params that follows (seen: a generic model evaluated with W = 0)
+  TRY(hipDeviceSynchronize());
 #undef TRY
   hh->tables_dirty = true;
   {
@@ -2290,17 +2299,24 @@ int resident_source(crbm_handle* h, int start, int end, RowSource* src) {
 // ---- double-buffered sweeps over host input ---------------------
 // Slab i is staged, encoded and processed on stream (i & 1) with buffer set (i & 1);
 // its outputs are collected only after slab i+1 has been enqueued, so the host->device
-// copy of one slab overlaps the kernels of the other.  Resident sources use set 0 only.
+// copy of one slab overlaps the kernels of the other.  Resident sources alternate too: slab i's outputs are still to be
+// copied out when slab i+1 runs, so the two must not share an output buffer.
+// Everything a slab writes belongs to its set: the staging and letter buffers, the outputs and the per-motif scratch of
+// the slabbed free energies (fe_scratch, in the slab model's shadow handle).  What the two streams share is read-only
+// during a sweep (parameters, d_tables and d_slab_tables: sweep_begin builds them first) or combined in any order
+// (d_flags: atomicOr; the hit summary's position sums: 64-bit integer atomics).
 struct SweepSet {
   hipStream_t st;
   DevBuf<float>* stage;
   DevBuf<uint32_t>* letters;
   DevBuf<float>* oa;
   DevBuf<float>* ob;
+  DevBuf<float>* fe_scratch;
 };
 SweepSet sweep_set(crbm_handle* h, int i) {
-  if (i & 1) return SweepSet{h->stream2, &h->stage2, &h->letters2, &h->out_a2, &h->out_b2};
-  return SweepSet{h->stream, &h->stage, &h->letters, &h->out_a, &h->out_b};
+  crbm_handle* s = h->slab;
+  if (i & 1) return SweepSet{h->stream2, &h->stage2, &h->letters2, &h->out_a2, &h->out_b2, s ? &s->out_b2 : nullptr};
+  return SweepSet{h->stream, &h->stage, &h->letters, &h->out_a, &h->out_b, s ? &s->out_b : nullptr};
 }
 // rows per slab: host input uses small slabs so that there is something to overlap
 int sweep_slab(const RowSource& src, size_t out_bytes_per_row) {
@@ -2342,10 +2358,15 @@ int sweep_rows(crbm_handle* h, const RowSource& src, int start, int cnt, const S
   HIPCHK(hipGetLastError());
   return CRBM_OK;
 }
-// tables built and visible to both streams before a sweep starts
+// tables built and visible to both streams before a sweep starts (the slab tables of a generic DNA model too: a slab on
+// the second stream must not find them being rebuilt on the main one)
 int sweep_begin(crbm_handle* h) {
   int rc = ensure_tables(h);
   if (rc) return rc;
+  if (h->slab) {
+    rc = slab_ensure_tables(h, h->stream);
+    if (rc) return rc;
+  }
   HIPCHK(hipStreamSynchronize(h->stream));
   return CRBM_OK;
 }
@@ -2384,7 +2405,7 @@ int launch_free_energy(crbm_handle* h, const uint32_t* rows, int n, int L, const
   if (rc) return rc;
   HIPCHK(set.oa->ensure((size_t)n));
   HIPCHK(set.ob->ensure((size_t)n * h->K));
-  if (h->big) return big_launch_eval(h, rows, n, L, 0, set.oa->p, set.ob->p, nullptr, nullptr, nullptr, set.st);
+  if (h->big) return big_launch_eval(h, rows, n, L, 0, set.oa->p, set.ob->p, nullptr, nullptr, nullptr, set.fe_scratch, set.st);
   FeArgs a;
   a.tables = h->d_tables;
   a.letters = rows;
@@ -2401,6 +2422,13 @@ int free_energy_any(crbm_handle* h, const RowSource& src, float* fe, float* fem)
   rc = sweep_begin(h);
   if (rc) return rc;
   const int slab = sweep_slab(src, ((size_t)h->K + 1) * sizeof(float));
+  if (slab_fe_on(h)) {
+    // the slabbed free energies' scratch of both sets at its largest before either stream starts: no ensure() inside the
+    // loop reallocates a buffer while kernels of the other stream run
+    const size_t scratch = (size_t)slab * h->slab->K * h->slab_n;
+    HIPCHK(h->slab->out_b.ensure(scratch));
+    if (slab < src.n) HIPCHK(h->slab->out_b2.ensure(scratch));
+  }
   int prev_start = -1, prev_cnt = 0;
   SweepSet prev = sweep_set(h, 0);
   auto collect = [&]() -> int {     // outputs of the previous slab -> host
@@ -2412,7 +2440,7 @@ int free_energy_any(crbm_handle* h, const RowSource& src, float* fe, float* fem)
   };
   for (int start = 0, i = 0; start < src.n; start += slab, ++i) {
     const int cnt = std::min(slab, src.n - start);
-    const SweepSet set = sweep_set(h, src.resident ? 0 : i);
+    const SweepSet set = sweep_set(h, i);
     const uint32_t* rows = nullptr;
     rc = sweep_rows(h, src, start, cnt, set, &rows);
     if (rc) return rc;
@@ -2494,7 +2522,7 @@ int hit_summary_any(crbm_handle* h, const RowSource& src, float* hmax, float* hm
   };
   for (int start = 0, i = 0; start < n; start += slab, ++i) {
     const int cnt = std::min(slab, n - start);
-    const SweepSet set = sweep_set(h, src.resident ? 0 : i);
+    const SweepSet set = sweep_set(h, i);
     const uint32_t* rows = nullptr;
     rc = sweep_rows(h, src, start, cnt, set, &rows);
     if (rc) return rc;
@@ -2514,7 +2542,7 @@ int hit_summary_any(crbm_handle* h, const RowSource& src, float* hmax, float* hm
     a.pos_fx = pos_fx;                          // both streams add (integers: any order)
     const unsigned gx = (unsigned)std::max(1, std::min((cnt + 3) / 4, std::max(1, h->num_cu * 8 / nchunks)));
     if (h->big) {
-      rc = big_launch_eval(h, rows, cnt, L, 1, nullptr, nullptr, a.hmax, a.hsum, pos_fx, set.st);
+      rc = big_launch_eval(h, rows, cnt, L, 1, nullptr, nullptr, a.hmax, a.hsum, pos_fx, nullptr, set.st);
       if (rc) return rc;
     } else
     HIPCHK(jit_launch(h->jk.hit_summary, a, gx, (unsigned)nchunks, 256, lds, set.st));
