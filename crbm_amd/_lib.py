@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libcrbm_hip.so")
 
 UNIQUE_ID_BYTES = 128
 IPC_HANDLE_BYTES = 64
-ABI_VERSION = 3          # CRBM_AMD_ABI_VERSION of include/crbm_amd.h
+ABI_VERSION = 4          # CRBM_AMD_ABI_VERSION of include/crbm_amd.h
 
 CRBM_OK = 0
 ERR_INVALID, ERR_HIP, ERR_NOT_ONEHOT, ERR_NOT_BINARY, ERR_RCCL, ERR_NO_GPU, ERR_IPC_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
@@ -53,6 +53,19 @@ _I32 = ctypes.c_int32
 _U32 = ctypes.c_uint32
 _U64 = ctypes.c_uint64
 _U8P = ctypes.POINTER(ctypes.c_uint8)
+_I64 = ctypes.c_int64
+_I32P = ctypes.POINTER(ctypes.c_int32)
+_I64P = ctypes.POINTER(ctypes.c_int64)
+
+
+class CrbmSite(ctypes.Structure):
+    """struct crbm_site (include/crbm_amd.h): 20 bytes, the layout of SITE_DTYPE."""
+    _fields_ = [("seq", ctypes.c_int32), ("motif", ctypes.c_int32), ("start", ctypes.c_int32),
+                ("strand", ctypes.c_int32), ("prob", ctypes.c_float)]
+
+
+_SITEP = ctypes.POINTER(CrbmSite)
+_SITES_TAIL = [ctypes.c_float, _I64, _SITEP, _I64P, _I32P, _I32P, _F]
 
 # name -> (restype, argtypes); every symbol declared in include/crbm_amd.h
 SIGNATURES = {
@@ -101,6 +114,9 @@ SIGNATURES = {
     "crbm_hit_summary": (_I32, [_H, _F, _I32, _I32, _F, _F, _F]),
     "crbm_hit_summary_codes": (_I32, [_H, _U8P, _I32, _I32, _F, _F, _F]),
     "crbm_hit_summary_resident": (_I32, [_H, _I32, _I32, _F, _F, _F]),
+    "crbm_motif_sites": (_I32, [_H, _F, _I32, _I32] + _SITES_TAIL),
+    "crbm_motif_sites_codes": (_I32, [_H, _U8P, _I32, _I32] + _SITES_TAIL),
+    "crbm_motif_sites_resident": (_I32, [_H, _I32, _I32] + _SITES_TAIL),
     "crbm_comm_unique_id": (_I32, [_U8P]),
     "crbm_comm_init": (_I32, [_H, _U8P, _I32, _I32]),
     "crbm_comm_destroy": (_I32, [_H]),

@@ -21,6 +21,9 @@ from . import _lib
 from ._lib import CrbmConfig, as_f32, fptr
 
 
+_RAW_SITE = np.dtype([("seq", "<i4"), ("motif", "<i4"), ("start", "<i4"), ("strand", "<i4"), ("prob", "<f4")])   # crbm_site
+
+
 class _DeviceShared(object):
     """Stand-in for a `theano.shared` variable (convRBM.py:133,149,152):
     `get_value()` / `set_value()` on a parameter that lives on the GPU."""
@@ -431,6 +434,67 @@ class CRBM(object):
         if position_mean:
             out["position_mean"] = pos
         return out
+
+    # motifSites() records: crbm_site of include/crbm_amd.h, with the strand narrowed to one byte
+    SITE_DTYPE = np.dtype([("seq", "<i4"), ("motif", "<i4"), ("start", "<i4"), ("strand", "i1"), ("prob", "<f4")])
+
+    @staticmethod
+    def _threshold(threshold):
+        t = float(threshold)
+        if not 0.0 <= t <= 1.0:          # (NaN too)
+            raise ValueError("threshold must lie in [0, 1], got %r" % (threshold,))
+        return t
+
+    def _sites_input(self, data):
+        """_input() (which checks the one-hot shape) and the sequence length, before any C call."""
+        got = self._input(data)
+        if got[3] < self.motif_length:
+            raise ValueError("sequences of length %d are shorter than motif_length %d" % (got[3], self.motif_length))
+        return got
+
+    def motifSites(self, data, threshold=0.5):
+        """Where the motifs occur: every (sequence, motif, position, strand) whose probability reaches
+        `threshold`, as a NumPy structured array (SITE_DTYPE: seq, motif, start, strand, prob) sorted by
+        (seq, motif, start, strand), + before -.  `start` is the 0-based hidden position; the site covers
+        letters [start, start + motif_length).  The score is that of motifHitProbs() (convRBM.py:507-514);
+        a double-stranded model also reports the reverse-complemented filter (strand -1; motifHitProbs has
+        the forward strand only), a single-stranded one has strand 0.  `data`: one-hot or (n, L) uint8 codes.
+        The records are gathered on the device without the dense (n,K,1,Lh) tensor; if there are more than
+        the first buffer takes, the whole pass is computed once more into a buffer of the exact size."""
+        t = self._threshold(threshold)
+        suffix, args, n, L, _keep = self._sites_input(data)
+        K, Lh = self.num_motifs, L - self.motif_length + 1
+        S = 2 if self.doublestranded else 1
+        count = ctypes.c_int64(0)
+
+        def call(capacity):
+            raw = np.empty(capacity, dtype=_RAW_SITE)
+            self._call("crbm_motif_sites" + suffix, *(args + (t, capacity, raw.ctypes.data_as(ctypes.POINTER(_lib.CrbmSite)),
+                                                             ctypes.byref(count), None, None, None)))
+            return raw
+        capacity = min(n * K * S * Lh, max(1 << 20, 4 * n * K))
+        raw = call(capacity)
+        if count.value > capacity:
+            raw = call(count.value)          # more sites than the first buffer took: the pass is computed again
+        raw = raw[:count.value]
+        out = np.empty(count.value, dtype=self.SITE_DTYPE)
+        for f in ("seq", "motif", "start", "strand", "prob"):
+            out[f] = raw[f]
+        return out
+
+    def motifBestSites(self, data):
+        """The best site of every (sequence, motif): dict of 'start' (n,K) int32, 'strand' (n,K) int8 and
+        'prob' (n,K) float32 -- the largest probability over positions and strands (motifSites' scores),
+        ties to the smaller start, then to +."""
+        suffix, args, n, L, _keep = self._sites_input(data)
+        K = self.num_motifs
+        start = np.empty((n, K), dtype=np.int32)
+        strand = np.empty((n, K), dtype=np.int32)
+        prob = np.empty((n, K), dtype=np.float32)
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        self._call("crbm_motif_sites" + suffix, *(args + (0.0, 0, None, None, start.ctypes.data_as(i32),
+                                                         strand.ctypes.data_as(i32), fptr(prob))))
+        return {"start": start, "strand": strand.astype(np.int8), "prob": prob}
 
     def freeEnergy(self, data, permotif=False):
         """convRBM.py:549-568 -> (n,) or (n,K); one-hot or (n,L) uint8 codes."""

@@ -166,6 +166,10 @@ struct crbm_handle {
   DevBuf<uint32_t> dataset[CRBM_DATASET_SLOTS];   // resident data sets (slot 0: training, slot 1: test by convention)
   DevBuf<float> partials, partials2;
   DevBuf<unsigned long long> eval_ones;            // sampled ones per mini-batch (crbm_eval_epoch_resident)
+  // motif sites (crbm_motif_sites*), one of each per set of a two-stream sweep: records, the slab's record counter,
+  // the best-site keys of the slab's (seq, motif)
+  DevBuf<SiteRec> site_recs[2];
+  DevBuf<unsigned long long> site_count[2], site_keys[2];
   float* d_sums = nullptr;
   int dataset_n[CRBM_DATASET_SLOTS] = {0, 0}, dataset_L[CRBM_DATASET_SLOTS] = {0, 0};
   int slot = 0;
@@ -1767,6 +1771,7 @@ int crbm_destroy(crbm_handle* h) {
   h->stage.release(); h->stage2.release(); h->out_a.release(); h->out_b.release(); h->out_c.release();
   h->letters.release(); h->letters2.release(); h->masks_tmp.release(); h->out_a2.release(); h->out_b2.release();
   for (auto& d : h->dataset) d.release(); h->partials.release(); h->partials2.release();
+  for (int i = 0; i < 2; ++i) { h->site_recs[i].release(); h->site_count[i].release(); h->site_keys[i].release(); }
   if (h->jk.module) (void)hipModuleUnload(h->jk.module);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -2569,6 +2574,164 @@ int hit_summary_any(crbm_handle* h, const RowSource& src, float* hmax, float* hm
   return CRBM_OK;
 }
 
+// ---- motif sites (crbm_motif_sites*) ------------------------------------------------------------------------------
+static_assert(sizeof(SiteRec) == sizeof(crbm_site) && sizeof(crbm_site) == 20, "crbm_site is the kernels' SiteRec");
+
+// records of one slab (seq within the slab) -> sorted by (seq, motif, start, strand), + before -: a counting pass over
+// the rows, then a sort of each row's few records
+void sort_sites(const std::vector<SiteRec>& in, int nrows, std::vector<SiteRec>* out) {
+  std::vector<size_t> first((size_t)nrows + 1, 0);
+  for (const SiteRec& r : in) ++first[(size_t)r.seq + 1];
+  for (int i = 0; i < nrows; ++i) first[i + 1] += first[i];
+  out->resize(in.size());
+  std::vector<size_t> at(first.begin(), first.end() - 1);
+  for (const SiteRec& r : in) (*out)[at[r.seq]++] = r;
+  auto before = [](const SiteRec& a, const SiteRec& b) {
+    if (a.motif != b.motif) return a.motif < b.motif;
+    if (a.start != b.start) return a.start < b.start;
+    return (a.strand < 0 ? 1 : 0) < (b.strand < 0 ? 1 : 0);
+  };
+  for (int i = 0; i < nrows; ++i)
+    if (first[i + 1] - first[i] > 1) std::sort(out->begin() + first[i], out->begin() + first[i + 1], before);
+}
+
+// Thresholded sites and best sites over a source, slab by slab on the two streams of a sweep.  Specialised models: the
+// fused crbm_motif_sites pass (motif_sites_body).  Generic models (h->big): the dense h|v of hit_probs_any into the set's
+// outputs (oa: the forward strand, or sigma(x + x') single-stranded; ob: the reverse-complemented filter), then
+// motif_sites_select_kernel.  Every set owns its records, counter and keys (sized before the loop); a slab whose count
+// exceeds its set's record buffer is run again into a larger one before anything is copied (its rows are still in the
+// set's buffers: the set is next used by the slab after the one enqueued before this collect).
+int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64_t capacity, crbm_site* sites,
+                    int64_t* count, int32_t* best_start, int32_t* best_strand, float* best_prob) {
+  ARGCHK(threshold >= 0.f && threshold <= 1.f, "threshold must lie in [0, 1]");   // (NaN fails both)
+  ARGCHK(capacity >= 0, "capacity must be >= 0");
+  ARGCHK(!sites || count, "count is required with sites");
+  const bool want_recs = sites != nullptr, want_best = best_start || best_strand || best_prob;
+  ARGCHK(want_recs || want_best, "null argument");
+  int rc = check_data_shape(h, src.n, src.L);
+  if (rc) return rc;
+  const int n = src.n, L = src.L, Lh = L - h->M + 1, K = h->K, S = h->ds ? 2 : 1;
+  const int PC = 64 * h->ms.HIT_NI;
+  const int nchunks = h->big ? 1 : (Lh + PC - 1) / PC;
+  const unsigned lds = h->big ? 0u : (unsigned)tab_bytes(h);
+  ARGCHK(h->big || lds <= 160u * 1024u, "model too large for the motif-site kernel");
+  rc = sweep_begin(h);
+  if (rc) return rc;
+  const size_t dense_per_row = h->big ? (size_t)S * K * Lh * sizeof(float) : 0;
+  const int slab = sweep_slab(src, (size_t)K * 8 + dense_per_row);
+  const int nsets = slab < n ? 2 : 1;
+  const size_t rec0 = std::min((size_t)slab * K * S * Lh, std::max<size_t>((size_t)1 << 16, (size_t)4 * slab * K));
+  for (int i = 0; i < nsets; ++i) {        // everything both streams write, at its size, before either starts
+    const SweepSet set = sweep_set(h, i);
+    if (want_recs) {
+      HIPCHK(h->site_recs[i].ensure(rec0));
+      HIPCHK(h->site_count[i].ensure(1));
+    }
+    if (want_best) HIPCHK(h->site_keys[i].ensure((size_t)slab * K));
+    if (h->big) {
+      HIPCHK(set.oa->ensure((size_t)slab * K * Lh));
+      if (S == 2) HIPCHK(set.ob->ensure((size_t)slab * K * Lh));
+    }
+  }
+  auto launch = [&](int i, const uint32_t* rows, int cnt) -> int {
+    const SweepSet set = sweep_set(h, i & 1);
+    SitesOut o;
+    o.recs = want_recs ? h->site_recs[i & 1].p : nullptr;
+    o.capacity = want_recs ? h->site_recs[i & 1].cap : 0;
+    o.count = want_recs ? h->site_count[i & 1].p : nullptr;
+    o.best = want_best ? h->site_keys[i & 1].p : nullptr;
+    o.threshold = threshold;
+    if (want_recs) HIPCHK(hipMemsetAsync(o.count, 0, sizeof(unsigned long long), set.st));
+    if (h->big) {
+      // convRBM.py:507-514 as hit_probs_any: doublestranded -> sigma(x) (and the flipped filter), else sigma(x + x')
+      int r = big_launch_hgv(h, rows, cnt, L, h->ds ? 0 : 2, nullptr, set.oa->p, nullptr, nullptr, nullptr, KIND_API_H, 0, 0, set.st);
+      if (!r && S == 2) r = big_launch_hgv(h, rows, cnt, L, 1, nullptr, set.ob->p, nullptr, nullptr, nullptr, KIND_API_H, 0, 0, set.st);
+      if (r) return r;
+      SitesSelectArgs a;
+      a.p0 = set.oa->p; a.p1 = S == 2 ? set.ob->p : nullptr;
+      a.n = cnt; a.K = K; a.Lh = Lh; a.ds = h->ds;
+      a.o = o;
+      hipLaunchKernelGGL(motif_sites_select_kernel, dim3(grid_for((long)cnt * K, 4, h->num_cu * 8)), dim3(256), 0, set.st, a);
+      HIPCHK(hipGetLastError());
+      return CRBM_OK;
+    }
+    if (want_best && nchunks > 1) HIPCHK(hipMemsetAsync(o.best, 0, (size_t)cnt * K * 8, set.st));   // (atomicMax across chunks)
+    SitesArgs a;
+    a.tables = h->d_tables; a.letters = rows;
+    a.n = cnt; a.L = L; a.Lh = Lh; a.LW = lw(h, L);
+    a.o = o;
+    const unsigned gx = (unsigned)std::max(1, std::min((cnt + 3) / 4, std::max(1, h->num_cu * 8 / nchunks)));
+    HIPCHK(jit_launch(h->jk.motif_sites, a, gx, (unsigned)nchunks, 256, lds, set.st));
+    return CRBM_OK;
+  };
+  int64_t total = 0;
+  int prev_i = -1, prev_start = 0, prev_cnt = 0;
+  const uint32_t* prev_rows = nullptr;
+  std::vector<SiteRec> raw, sorted;
+  std::vector<unsigned long long> keys;
+  auto collect = [&]() -> int {
+    if (prev_i < 0) return CRBM_OK;
+    const int si = prev_i & 1;
+    const SweepSet set = sweep_set(h, si);
+    if (want_best) {
+      keys.resize((size_t)prev_cnt * K);
+      HIPCHK(hipMemcpyAsync(keys.data(), h->site_keys[si].p, keys.size() * 8, hipMemcpyDeviceToHost, set.st));
+    }
+    unsigned long long c = 0;
+    if (want_recs) HIPCHK(hipMemcpyAsync(&c, h->site_count[si].p, sizeof(c), hipMemcpyDeviceToHost, set.st));
+    HIPCHK(hipStreamSynchronize(set.st));
+    if (want_recs && total < capacity) {
+      if (c > h->site_recs[si].cap) {       // more records than the set's buffer took: again, into one that takes them
+        HIPCHK(h->site_recs[si].ensure((size_t)c));
+        rc = launch(prev_i, prev_rows, prev_cnt);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(set.st));
+      }
+      raw.resize((size_t)c);
+      HIPCHK(hipMemcpyAsync(raw.data(), h->site_recs[si].p, (size_t)c * sizeof(SiteRec), hipMemcpyDeviceToHost, set.st));
+      HIPCHK(hipStreamSynchronize(set.st));
+      sort_sites(raw, prev_cnt, &sorted);
+      const size_t keep = (size_t)std::min<int64_t>((int64_t)c, capacity - total);
+      for (size_t r = 0; r < keep; ++r) {
+        const SiteRec& x = sorted[r];
+        sites[total + (int64_t)r] = crbm_site{x.seq + prev_start, x.motif, x.start, x.strand, x.prob};
+      }
+    }
+    total += (int64_t)c;
+    if (want_best) {
+      for (size_t r = 0; r < keys.size(); ++r) {
+        const size_t o = (size_t)prev_start * K + r;
+        const uint32_t code = 0xFFFFFFFFu - (uint32_t)keys[r];
+        float p;
+        const uint32_t bits = (uint32_t)(keys[r] >> 32);
+        std::memcpy(&p, &bits, 4);
+        if (best_start) best_start[o] = (int32_t)(code >> 1);
+        if (best_strand) best_strand[o] = h->ds ? ((code & 1u) ? -1 : 1) : 0;
+        if (best_prob) best_prob[o] = p;
+      }
+    }
+    return CRBM_OK;
+  };
+  for (int start = 0, i = 0; start < n; start += slab, ++i) {
+    const int cnt = std::min(slab, n - start);
+    const SweepSet set = sweep_set(h, i);
+    const uint32_t* rows = nullptr;
+    rc = sweep_rows(h, src, start, cnt, set, &rows);
+    if (rc) return rc;
+    rc = launch(i, rows, cnt);
+    if (rc) return rc;
+    rc = collect();
+    if (rc) return rc;
+    prev_i = i; prev_start = start; prev_cnt = cnt; prev_rows = rows;
+  }
+  rc = collect();
+  if (rc) return rc;
+  rc = sweep_finish(h, src);
+  if (rc) return rc;
+  if (count) *count = want_recs ? total : 0;
+  return CRBM_OK;
+}
+
 static RowSource host_onehot_(const float* v, int n, int L, int A) { RowSource s; s.onehot = v; s.n = n; s.L = L; s.A = A; return s; }
 static RowSource host_codes_(const uint8_t* c, int n, int L, int A) { RowSource s; s.codes = c; s.n = n; s.L = L; s.A = A; return s; }
 #define host_onehot(v, n, L) host_onehot_(v, n, L, h->A)
@@ -2707,6 +2870,30 @@ int crbm_hit_summary_resident(crbm_handle* h, int32_t start, int32_t end, float*
   int rc = resident_source(h, start, end, &src);
   if (rc) return rc;
   return hit_summary_any(h, src, hit_max, hit_mean, position_mean);
+}
+
+int crbm_motif_sites(crbm_handle* h, const float* v, int32_t n, int32_t L, float threshold, int64_t capacity,
+                     crbm_site* sites, int64_t* count, int32_t* best_start, int32_t* best_strand, float* best_prob) {
+  ENTER();
+  ARGCHK(v, "null argument");
+  return motif_sites_any(h, host_onehot(v, n, L), threshold, capacity, sites, count, best_start, best_strand, best_prob);
+}
+
+int crbm_motif_sites_codes(crbm_handle* h, const uint8_t* codes, int32_t n, int32_t L, float threshold, int64_t capacity,
+                           crbm_site* sites, int64_t* count, int32_t* best_start, int32_t* best_strand, float* best_prob) {
+  ENTER();
+  ARGCHK(codes, "null argument");
+  return motif_sites_any(h, host_codes(codes, n, L), threshold, capacity, sites, count, best_start, best_strand, best_prob);
+}
+
+int crbm_motif_sites_resident(crbm_handle* h, int32_t start, int32_t end, float threshold, int64_t capacity,
+                              crbm_site* sites, int64_t* count, int32_t* best_start, int32_t* best_strand,
+                              float* best_prob) {
+  ENTER();
+  RowSource src;
+  int rc = resident_source(h, start, end, &src);
+  if (rc) return rc;
+  return motif_sites_any(h, src, threshold, capacity, sites, count, best_start, best_strand, best_prob);
 }
 
 int crbm_eval_params(crbm_handle* h, float* twn, float* ic, float* medic) {

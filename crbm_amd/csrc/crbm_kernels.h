@@ -113,6 +113,10 @@ __device__ __forceinline__ floatx4 mfma_16x16x32_f16(const HalfFrag& a, const Ha
 typedef float floatx2 __attribute__((vector_size(8)));
 __device__ __forceinline__ floatx2 fma2(floatx2 a, floatx2 b, floatx2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ floatx2 opaque(floatx2 v) { asm volatile("" : "+v"(v)); return v; }
+// lanes of `mask` below this lane (v_mbcnt_lo / v_mbcnt_hi)
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
 #else   // CPU emulation build (tests/emu/shim/hip/hip_runtime.h implements the wave-wide parts)
 typedef float floatx4 __attribute__((vector_size(16)));
 typedef float floatx2 __attribute__((vector_size(8)));
@@ -142,6 +146,13 @@ __device__ __forceinline__ void short_sleep() {}
 __device__ __forceinline__ uint64_t realtime_ticks() { return emu::realtime_ticks(); }   // microseconds
 __device__ __forceinline__ uint64_t shader_cycles() { return emu::realtime_ticks(); }
 __device__ __forceinline__ void split_f16(const float (&x)[8], HalfFrag& hi, HalfFrag& lo) { emu::split_f16(x, hi.r, lo.r); }
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
+  return (uint32_t)__popcll(mask & ((1ull << (threadIdx.x & 63u)) - 1ull));
+}
+}  // namespace crbm
+// supplied by the driver that runs the motif-site kernels (tests/emu/emu_sites.cpp); nothing else calls it
+unsigned long long atomicMax(unsigned long long* p, unsigned long long v);
+namespace crbm {
 __device__ __forceinline__ floatx4 mfma_16x16x32_f16(const HalfFrag& a, const HalfFrag& b, floatx4 c) {
   float d[4] = {c[0], c[1], c[2], c[3]};
   emu::mfma_16x16x32_f16(a.r, b.r, d);
@@ -262,6 +273,21 @@ __device__ __forceinline__ float wave_max_nonneg(float v) {
   v = fmaxf(v, dpp_move<0x142, 0xa>(v));
   v = fmaxf(v, dpp_move<0x143, 0xc>(v));
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
+// maximum of unsigned integers, the same DPP moves (0 is the identity here too)
+__device__ __forceinline__ uint32_t umax32(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+  auto move = [](uint32_t x, auto CTRL, auto ROW_MASK) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, decltype(CTRL)::value, decltype(ROW_MASK)::value, 0xf, false);
+  };
+  v = umax32(v, move(v, IC<0x121>{}, IC<0xf>{}));
+  v = umax32(v, move(v, IC<0x122>{}, IC<0xf>{}));
+  v = umax32(v, move(v, IC<0x124>{}, IC<0xf>{}));
+  v = umax32(v, move(v, IC<0x128>{}, IC<0xf>{}));
+  v = umax32(v, move(v, IC<0x142>{}, IC<0xa>{}));
+  v = umax32(v, move(v, IC<0x143>{}, IC<0xc>{}));
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
 // ---------------------------------------------------------------------------
@@ -924,10 +950,13 @@ __device__ __forceinline__ float stats_window_piece(unsigned short* win16, int t
 }
 
 // z[] = the gather of motif quads [q0, q0 + NQW) (clamped to the model's NQ); z = -log2(e) * activation
-template <class C, int NQW>
+// ACCUMULATE: z[] (+)= the gather instead, every group added in turn (conv_gather's order: the same sums to the bit)
+template <class C, int NQW, bool ACCUMULATE = false>
 __device__ __forceinline__ void conv_gather_quads(const float* T, const LetterWin<C::M>& win, int q0, float (&z)[4 * NQW]) {
+  if (!ACCUMULATE) {
 #pragma unroll
-  for (int i = 0; i < 4 * NQW; ++i) z[i] = 0.f;   // quads beyond the model's NQ
+    for (int i = 0; i < 4 * NQW; ++i) z[i] = 0.f;   // quads beyond the model's NQ
+  }
   auto group = [&](int g, auto FIRST) {
     constexpr bool first = decltype(FIRST)::value != 0;   // the first group assigns
     const uint32_t r = window_bits<C::M>(win, 2 * C::G * g) & (uint32_t)(C::ROWS - 1);
@@ -943,7 +972,7 @@ __device__ __forceinline__ void conv_gather_quads(const float* T, const LetterWi
         }
       }
   };
-  group(0, IC<1>{});
+  if (ACCUMULATE) group(0, IC<0>{}); else group(0, IC<1>{});
   if constexpr (C::NG * NQW <= 48) {
 #pragma unroll
     for (int g = 1; g < C::NG; ++g) group(g, IC<0>{});
@@ -2026,6 +2055,198 @@ __device__ void hit_summary_body(const HitArgs& a) {
   }
 }
 
+// ===========================================================================
+// Motif sites (crbm_motif_sites*): every (sequence, motif, position, strand) whose pooled probability reaches a
+// threshold, as a compact list of records, and the best site of every (sequence, motif) -- without the dense
+// (n,K,1,Lh) tensor of motifHitProbs() (convRBM.py:507-514).  Scores: single-stranded models sigma-pool(x + x')
+// (what motifHitProbs reports, strand 0), double-stranded ones the forward strand (+1, what motifHitProbs reports)
+// and the reverse-complemented filter (-1, the forward gather of the reverse-complemented window: revcomp_window).
+//   records: a wave reserves the slots of its hits with ONE 64-bit atomicAdd on the slab's counter (per sequence and
+//            position chunk in the fused pass, per step in the select pass) and every lane writes its hits at base +
+//            (hits of earlier motifs) + (hits of lower lanes); records land only below `capacity`, the counter keeps
+//            counting past it.  Their order is the order of the atomics: the
+//            host sorts them (crbm_api.hip, motif_sites_any).
+//   best:    one 64-bit key per (sequence, motif), prob bits on top (probabilities are >= 0: their bits order like
+//            integers) and ~(2 start + strand_bit) below, so that the largest key is the largest probability, then
+//            the smaller start, then + before -.  Reduced per wave, stored directly when the positions of a sequence
+//            are one chunk, atomicMax (zero-initialised keys; a real key is never 0) across chunks.
+// No float is ever combined across threads: every number is a per-position probability, the same bits in every run.
+// ===========================================================================
+struct SiteRec {      // crbm_site of include/crbm_amd.h
+  int32_t seq, motif, start, strand;
+  float prob;
+};
+struct SitesOut {
+  SiteRec* recs;                 // records, or null (no list)
+  unsigned long long capacity;   // records `recs` holds
+  unsigned long long* count;     // the slab's counter (zero-initialised), exact past capacity
+  unsigned long long* best;      // (n,K) keys, or null
+  float threshold;
+};
+struct SitesArgs {
+  const float* tables;
+  const uint32_t* letters;
+  int32_t n, L, Lh, LW;
+  SitesOut o;
+};
+__device__ __forceinline__ unsigned long long site_key(float p, int start, int strand_bit) {
+  return ((unsigned long long)__float_as_uint(p) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(2 * start + strand_bit));
+}
+// the larger key of the wave (all lanes call it; every lane gets it)
+__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long key) {
+  const uint32_t hi = wave_max_u32((uint32_t)(key >> 32));
+  const uint32_t lo = wave_max_u32((uint32_t)(key >> 32) == hi ? (uint32_t)key : 0u);
+  return ((unsigned long long)hi << 32) | lo;
+}
+// hits of NS candidates per lane over the wave (all lanes call it)
+template <int NS>
+__device__ __forceinline__ uint32_t count_sites(const bool (&hit)[NS]) {
+  uint32_t tot = 0;
+#pragma unroll
+  for (int j = 0; j < NS; ++j) tot += (uint32_t)__popcll(__ballot(hit[j]));
+  return tot;
+}
+// `tot` slots of the slab's record list for the wave: one atomicAdd (lane 0), the base handed to every lane
+__device__ __forceinline__ unsigned long long reserve_sites(const SitesOut& o, uint32_t tot) {
+  unsigned long long base = 0;
+  if ((threadIdx.x & 63) == 0) base = atomicAdd(o.count, (unsigned long long)tot);
+  return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(base >> 32), 0) << 32) |
+         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)base, 0);
+}
+// Records of NS candidates per lane into reserved slots from `base` on (all lanes of the wave call it with the same
+// NS); hit[j] says whether this lane's candidate j is a site, rec(j) makes its record.  Slot order: candidate j, then
+// lane.  `base` moves past the wave's hits.
+template <int NS, class RecFun>
+__device__ __forceinline__ void write_sites(const SitesOut& o, const bool (&hit)[NS], RecFun rec, unsigned long long& base) {
+  unsigned long long m[NS];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) m[j] = __ballot(hit[j]);
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    const unsigned long long idx = base + lanes_below(m[j]);
+    if (hit[j] && idx < o.capacity) {
+      const SiteRec r = rec(j);
+      SiteRec* d = o.recs + idx;
+      d->seq = r.seq; d->motif = r.motif; d->start = r.start; d->strand = r.strand; d->prob = r.prob;
+    }
+    base += (unsigned long long)__popcll(m[j]);
+  }
+}
+// reserve_sites + write_sites for one step
+template <int NS, class RecFun>
+__device__ __forceinline__ void emit_sites(const SitesOut& o, const bool (&hit)[NS], RecFun rec) {
+  const uint32_t tot = count_sites<NS>(hit);
+  if (tot == 0) return;                                      // wave-uniform
+  unsigned long long base = reserve_sites(o, tot);
+  write_sites<NS>(o, hit, rec, base);
+}
+
+// The fused pass of the specialised models: hit_summary_body's geometry (one wave per sequence, a lane owns HIT_NI
+// positions of the chunk blockIdx.y of 64*HIT_NI positions), the motifs in groups of NQW quads (registers stay bounded
+// at any K: no float[KP] per lane), per group the positions, per position the strands.  With a record list the wave
+// walks its sequence twice: it counts its hits, reserves their slots with ONE atomicAdd, then writes them (one atomic
+// per step on the one counter serialised the kernel: 58 ms instead of 2 at 10^6 x 200 bp and ~1 site per motif).
+template <class C>
+__device__ void motif_sites_body(const SitesArgs& a) {
+  constexpr int K = C::K, M = C::M, NI = C::HIT_NI, PC = 64 * NI;
+  constexpr int NQW = C::NQ < 4 ? C::NQ : 4, NV = 4 * NQW;
+  constexpr bool BOTH = !C::DS;   // single-stranded models score sigma(x + x'), convRBM.py:511-514
+  constexpr int S = C::DS ? 2 : 1;
+  HIP_DYNAMIC_SHARED(float, smem);
+  float* Tf = smem;
+  copy_tables<C::TAB>(Tf, a.tables + C::OFF_TF);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const int s0 = blockIdx.y * PC;
+  const bool want_recs = a.o.recs != nullptr, want_best = a.o.best != nullptr;
+  const float thr = a.o.threshold;
+  for (int nn = blockIdx.x * nwaves + wave; nn < a.n; nn += gridDim.x * nwaves) {
+    const uint32_t* row = a.letters + (size_t)nn * a.LW;
+    // p[] = the scores of motifs [4 q0, 4 q0 + NV) at position s on `strand` (0 where s is past the sequence)
+    auto scores = [&](int q0, int s, int strand, float (&p)[NV]) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) p[j] = 0.f;
+      if (s >= a.Lh) return;
+      auto zfun = [&](int pos, float (&zz)[NV]) {
+        const LetterWin<M> w = letter_window<M>(row, pos);
+        conv_gather_quads<C, NQW>(Tf, strand ? revcomp_window<M>(w) : w, q0, zz);
+        if (BOTH) conv_gather_quads<C, NQW, true>(Tf, revcomp_window<M>(w), q0, zz);
+      };
+      if constexpr (C::POOL > 1) {
+        float cb[NV], Sg[NV];
+        pooled_probs<C::POOL, NV>(zfun, s, p, cb, Sg);
+      } else {
+        float z[NV];
+        zfun(s, z);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) p[j] = sigmoid_z(z[j]);
+      }
+    };
+    auto hits = [&](int q0, int s, const float (&p)[NV], bool (&hit)[NV]) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) hit[j] = s < a.Lh && 4 * q0 + j < K && p[j] >= thr;
+    };
+    unsigned long long base = 0;
+    if (want_recs) {
+      uint32_t tot = 0;
+#pragma unroll 1
+      for (int q0 = 0; q0 < C::NQ; q0 += NQW)
+#pragma unroll 1
+        for (int i = 0; i < NI; ++i)
+#pragma unroll 1
+          for (int strand = 0; strand < S; ++strand) {
+            float p[NV];
+            bool hit[NV];
+            scores(q0, s0 + lane + 64 * i, strand, p);
+            hits(q0, s0 + lane + 64 * i, p, hit);
+            tot += count_sites<NV>(hit);
+          }
+      if (tot == 0 && !want_best) continue;                // wave-uniform
+      if (tot) base = reserve_sites(a.o, tot);
+    }
+#pragma unroll 1
+    for (int q0 = 0; q0 < C::NQ; q0 += NQW) {
+      unsigned long long key[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) key[j] = 0ull;
+#pragma unroll 1
+      for (int i = 0; i < NI; ++i) {
+        const int s = s0 + lane + 64 * i;
+#pragma unroll 1
+        for (int strand = 0; strand < S; ++strand) {
+          float p[NV];
+          scores(q0, s, strand, p);
+          if (want_recs) {
+            const int sign = C::DS ? (strand ? -1 : 1) : 0;
+            bool hit[NV];
+            hits(q0, s, p, hit);
+            write_sites<NV>(a.o, hit, [&](int j) { return SiteRec{nn, 4 * q0 + j, s, sign, p[j]}; }, base);
+          }
+          if (want_best && s < a.Lh) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+              const unsigned long long k = site_key(p[j], s, strand);
+              key[j] = k > key[j] ? k : key[j];
+            }
+          }
+        }
+      }
+      if (want_best) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+          if (4 * q0 + j >= K) continue;                        // wave-uniform
+          const unsigned long long k = wave_max_key(key[j]);
+          if (lane == 0) {
+            unsigned long long* dst = a.o.best + (size_t)nn * K + 4 * q0 + j;
+            if (gridDim.y == 1) *dst = k;
+            else atomicMax(dst, k);
+          }
+        }
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Normalise the (all-reduced) raw sums and apply the SGD+momentum update
 // (convRBM.py:358-371, :415-436, :440-451).
@@ -2759,6 +2980,50 @@ __global__ void __launch_bounds__(256) vgh_dense_any_kernel(VghAnyArgs aa) {
 __global__ void hit_finalize_kernel(const unsigned long long* fx, float* out, size_t count, float scale) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
     out[i] = (float)((double)fx[i] * (double)scale);
+}
+
+// Motif sites of the models the fused pass does not take (crbm_api.hip, motif_sites_any on h->big): the same records and
+// keys (emit_sites, site_key) from the dense probabilities of a slab, p0 = the forward strand (single-stranded models:
+// sigma-pool(x + x')), p1 = the reverse-complemented filter or null.  One wave per (sequence, motif) row: the key is
+// stored, no atomics but the record counter's.
+struct SitesSelectArgs {
+  const float* p0;
+  const float* p1;
+  int32_t n, K, Lh, ds;
+  SitesOut o;
+};
+__global__ void __launch_bounds__(256) motif_sites_select_kernel(SitesSelectArgs a) {
+  const int lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
+  const long rows = (long)a.n * a.K;
+  for (long r = (long)blockIdx.x * nwaves + (threadIdx.x >> 6); r < rows; r += (long)gridDim.x * nwaves) {
+    const int nn = (int)(r / a.K), k = (int)(r - (long)nn * a.K);
+    unsigned long long key = 0ull;
+    for (int s0 = 0; s0 < a.Lh; s0 += 64) {
+      const int s = s0 + lane;
+      const bool valid = s < a.Lh;
+      float p[2] = {0.f, 0.f};
+      if (valid) {
+        p[0] = a.p0[(size_t)r * a.Lh + s];
+        if (a.p1) p[1] = a.p1[(size_t)r * a.Lh + s];
+      }
+      if (a.o.recs) {
+        const bool hit[2] = {valid && p[0] >= a.o.threshold, valid && a.p1 && p[1] >= a.o.threshold};
+        emit_sites<2>(a.o, hit, [&](int j) { return SiteRec{nn, k, s, a.ds ? (j ? -1 : 1) : 0, p[j]}; });
+      }
+      if (valid) {
+        const unsigned long long k0 = site_key(p[0], s, 0);
+        key = k0 > key ? k0 : key;
+        if (a.p1) {
+          const unsigned long long k1 = site_key(p[1], s, 1);
+          key = k1 > key ? k1 : key;
+        }
+      }
+    }
+    if (a.o.best) {
+      const unsigned long long kmax = wave_max_key(key);
+      if (lane == 0) a.o.best[r] = kmax;
+    }
+  }
 }
 
 // One wave that does nothing for `ticks` of the GPU's wall clock: put in front of a partition's first chain launch

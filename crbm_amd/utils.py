@@ -1,4 +1,4 @@
-"""Motif export.
+"""Motif export and motif-site export.
 
 secomo/utils.py:16-47 writes one file per motif through Bio.motifs.jaspar;
 this writer produces the same text layouts without Biopython.  The plotting
@@ -35,3 +35,25 @@ def saveMotifs(model, path, name="mot", fformat="jaspar"):
     for i, pfm in enumerate(pfms):
         with open(os.path.join(path, "{}{:d}.{}".format(name, i, "pfm")), "w") as f:
             f.write(formatMotif(pfm, name + str(i + 1), fformat))
+
+
+_STRAND = {1: "+", -1: "-", 0: "."}
+
+
+def saveSites(model, sites, filename, names=None, fformat="bed", name="mot"):
+    """Write the records of CRBM.motifSites() to `filename`.  'bed': BED6 lines
+    chrom, start, end = start + motif_length, name, score = prob, strand (+ - .),
+    with chrom = names[seq] (e.g. the FASTA record ids) or 'seq<i>' and the motif
+    named like saveMotifs' headers (<name><k+1>); 'tab': the same fields under a
+    header line."""
+    if fformat not in ("bed", "tab"):
+        raise ValueError("Unknown site format %s" % fformat)
+    M = model.motif_length
+    lines = ["chrom\tstart\tend\tmotif\tprob\tstrand"] if fformat == "tab" else []
+    for r in sites:
+        seq, k, start = int(r["seq"]), int(r["motif"]), int(r["start"])
+        chrom = names[seq] if names is not None else "seq{:d}".format(seq)
+        lines.append("\t".join([chrom, str(start), str(start + M), "{}{:d}".format(name, k + 1),
+                                "{:.6g}".format(float(r["prob"])), _STRAND[int(r["strand"])]]))
+    with open(filename, "w") as f:
+        f.write("".join(line + "\n" for line in lines))

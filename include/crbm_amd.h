@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CRBM_AMD_ABI_VERSION 3
+#define CRBM_AMD_ABI_VERSION 4
 
 typedef enum crbm_status {
   CRBM_OK = 0,
@@ -199,6 +199,31 @@ int crbm_hit_summary_codes(crbm_handle* h, const uint8_t* codes, int32_t n, int3
                            float* hit_mean, float* position_mean);
 int crbm_hit_summary_resident(crbm_handle* h, int32_t start, int32_t end, float* hit_max, float* hit_mean,
                               float* position_mean);
+
+/* ---- motif sites --------------------------------------------------------------
+ * WHERE the motifs occur, without the dense (n,K,1,Lh) tensor of crbm_hit_probs.  The score of a hidden position is
+ * the pooled probability of theano_getHitProbs (convRBM.py:507-514): single-stranded models have one per position,
+ * sigma-pool(x + x'), strand 0; double-stranded models have two, the forward strand (+1, what crbm_hit_probs
+ * reports) and the reverse-complemented filter (-1, _computeHgivenV(data, flip) of :269-275).
+ * A site is a record with prob >= threshold (threshold in [0,1], else CRBM_ERR_INVALID); `start` is the hidden
+ * position 0..L-M, the site covers letters [start, start+M); `seq` counts rows of the call (from `start` of the
+ * resident form).  Records come sorted by (seq, motif, start, strand), + before -, the same bits in every run, for
+ * every input form and every CRBM_SLAB_BYTES.  At most `capacity` of them are written to `sites`; `*count` is always
+ * the exact total (threshold 0: n*K*S*(L-M+1), S = 2 double-stranded, else 1).  sites == NULL: no records, nothing
+ * counted (count may then be NULL too).
+ * Best site of every (seq, motif), (n,K) each: the largest prob over positions and strands, ties to the smaller start,
+ * then to +.  best_start / best_strand / best_prob may each be NULL; all three NULL skips that work. */
+typedef struct crbm_site {
+  int32_t seq, motif, start, strand;   /* strand: +1, -1, or 0 (single-stranded model) */
+  float prob;
+} crbm_site;
+int crbm_motif_sites(crbm_handle* h, const float* v, int32_t n, int32_t L, float threshold, int64_t capacity,
+                     crbm_site* sites, int64_t* count, int32_t* best_start, int32_t* best_strand, float* best_prob);
+int crbm_motif_sites_codes(crbm_handle* h, const uint8_t* codes, int32_t n, int32_t L, float threshold, int64_t capacity,
+                           crbm_site* sites, int64_t* count, int32_t* best_start, int32_t* best_strand, float* best_prob);
+int crbm_motif_sites_resident(crbm_handle* h, int32_t start, int32_t end, float threshold, int64_t capacity,
+                              crbm_site* sites, int64_t* count, int32_t* best_start, int32_t* best_strand,
+                              float* best_prob);
 
 /* ---- data-parallel (new: the reference is single-device) -----------------
  * One process per GPU.  Rank 0 calls crbm_comm_unique_id and distributes the
