@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libcrbm_hip.so")
 
 UNIQUE_ID_BYTES = 128
 IPC_HANDLE_BYTES = 64
-ABI_VERSION = 4          # CRBM_AMD_ABI_VERSION of include/crbm_amd.h
+ABI_VERSION = 5          # CRBM_AMD_ABI_VERSION of include/crbm_amd.h
 
 CRBM_OK = 0
 ERR_INVALID, ERR_HIP, ERR_NOT_ONEHOT, ERR_NOT_BINARY, ERR_RCCL, ERR_NO_GPU, ERR_IPC_TIMEOUT = -1, -2, -3, -4, -5, -6, -7
@@ -44,7 +44,8 @@ class CrbmConfig(ctypes.Structure):
 class CrbmLaunchInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "nq", "group", "gibbs_grid", "gibbs_block", "gibbs_seqs_per_tile", "gibbs_lds_bytes",
-        "stats_grid_x", "stats_grid_y", "stats_block", "stats_lds_bytes", "gibbs_sparse", "activity_ppm", "stats_fused", "chain_parts")]
+        "stats_grid_x", "stats_grid_y", "stats_block", "stats_lds_bytes", "gibbs_sparse", "activity_ppm", "stats_fused", "chain_parts",
+        "mutagenesis_route")]
 
 
 _H = ctypes.c_void_p
@@ -117,6 +118,9 @@ SIGNATURES = {
     "crbm_motif_sites": (_I32, [_H, _F, _I32, _I32] + _SITES_TAIL),
     "crbm_motif_sites_codes": (_I32, [_H, _U8P, _I32, _I32] + _SITES_TAIL),
     "crbm_motif_sites_resident": (_I32, [_H, _I32, _I32] + _SITES_TAIL),
+    "crbm_mutagenesis": (_I32, [_H, _F, _I32, _I32, _F, _F]),
+    "crbm_mutagenesis_codes": (_I32, [_H, _U8P, _I32, _I32, _F, _F]),
+    "crbm_mutagenesis_resident": (_I32, [_H, _I32, _I32, _F, _F]),
     "crbm_comm_unique_id": (_I32, [_U8P]),
     "crbm_comm_init": (_I32, [_H, _U8P, _I32, _I32]),
     "crbm_comm_destroy": (_I32, [_H]),

@@ -496,6 +496,26 @@ class CRBM(object):
                                                          strand.ctypes.data_as(i32), fptr(prob))))
         return {"start": start, "strand": strand.astype(np.int8), "prob": prob}
 
+    def mutagenesis(self, data):
+        """In-silico mutagenesis: (n, L, input_dims) float32, dF[n, p, a] = F(sequence n with letter p replaced by a)
+        - F(sequence n) with F = L * freeEnergy, the unnormalised free energy (convRBM.py:657-676).  The entry of
+        the sequence's own letter is exactly 0; negative means the substitution fits the model better.  Only the
+        windows that cover p are evaluated; the mutated sequences are never built on the host.
+        `data`: one-hot or (n, L) uint8 codes."""
+        suffix, args, n, L, _keep = self._sites_input(data)
+        out = np.empty((n, L, self.input_dims), dtype=np.float32)
+        self._call("crbm_mutagenesis" + suffix, *(args + (fptr(out), None)))
+        return out
+
+    def pseudoLogLikelihood(self, data):
+        """(n,) float32: sum over positions of log P(v_p | all other letters) = sum_p -log sum_a exp(-dF[n, p, a]) with
+        dF of mutagenesis(); <= 0, larger is a better fit.  The dense (n, L, input_dims) array is not formed.
+        `data`: one-hot or (n, L) uint8 codes."""
+        suffix, args, n, L, _keep = self._sites_input(data)
+        out = np.empty((n,), dtype=np.float32)
+        self._call("crbm_mutagenesis" + suffix, *(args + (None, fptr(out))))
+        return out
+
     def freeEnergy(self, data, permotif=False):
         """convRBM.py:549-568 -> (n,) or (n,K); one-hot or (n,L) uint8 codes."""
         suffix, args, n, L, _keep = self._input(data)

@@ -170,6 +170,11 @@ struct crbm_handle {
   // the best-site keys of the slab's (seq, motif)
   DevBuf<SiteRec> site_recs[2];
   DevBuf<unsigned long long> site_count[2], site_keys[2];
+  // in-silico mutagenesis (crbm_mutagenesis*), one of each per set of a two-stream sweep: dF and pll of a slab, and the
+  // expanded rows (base rows and their single-substitution copies) of the general path
+  DevBuf<float> mut_df[2], mut_pll[2];
+  DevBuf<uint32_t> mut_rows[2];
+  int mut_route = 0;                               // route of the last crbm_mutagenesis* call: 1 fused kernel, 2 general path
   float* d_sums = nullptr;
   int dataset_n[CRBM_DATASET_SLOTS] = {0, 0}, dataset_L[CRBM_DATASET_SLOTS] = {0, 0};
   int slot = 0;
@@ -1772,6 +1777,7 @@ int crbm_destroy(crbm_handle* h) {
   h->letters.release(); h->letters2.release(); h->masks_tmp.release(); h->out_a2.release(); h->out_b2.release();
   for (auto& d : h->dataset) d.release(); h->partials.release(); h->partials2.release();
   for (int i = 0; i < 2; ++i) { h->site_recs[i].release(); h->site_count[i].release(); h->site_keys[i].release(); }
+  for (int i = 0; i < 2; ++i) { h->mut_df[i].release(); h->mut_pll[i].release(); h->mut_rows[i].release(); }
   if (h->jk.module) (void)hipModuleUnload(h->jk.module);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -2732,6 +2738,110 @@ int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64
   return CRBM_OK;
 }
 
+// ---- in-silico mutagenesis (crbm_mutagenesis*) ----------------------------------------------------------------------
+// dF (n,L,A) and / or pll (n) over a source, slab by slab on the two streams of a sweep.  Specialised models without
+// pooling: the fused crbm_mutagenesis pass (mutagenesis_body; as many waves per block as the LDS holds accumulators
+// beside the tables).  Everything else -- pooled models, generic models, CRBM_MUT_FUSED=0, sequences whose accumulator
+// does not fit beside the tables -- takes the general path: mutagenesis_expand_kernel writes the slab's base rows and
+// their (A-1) L copies, the class's own free-energy launch (launch_free_energy) leaves their per-motif terms in the
+// set's outputs, mutagenesis_combine_kernel forms dF and pll.  Every set owns what it writes, sized before the loop;
+// the slab comes from the slab budget with the copies, their free energies and the outputs counted per row.
+int mutagenesis_any(crbm_handle* h, const RowSource& src, float* dfe, float* pll) {
+  ARGCHK(dfe || pll, "null argument");
+  int rc = check_data_shape(h, src.n, src.L);
+  if (rc) return rc;
+  const int n = src.n, L = src.L, A = h->A, K = h->K, LW = lw(h, L);
+  int waves = 0;
+  if (!h->big && h->ms.POOL == 1 && env_int("CRBM_MUT_FUSED", 1) != 0)
+    for (waves = 4; waves >= 1; waves >>= 1)
+      if ((size_t)tab_bytes(h) + (size_t)waves * 3 * mut_plane(L) * sizeof(float) <= 160u * 1024u) break;
+  const bool fused = waves >= 1;
+  const unsigned lds = fused ? (unsigned)(tab_bytes(h) + waves * 3 * mut_plane(L) * (int)sizeof(float)) : 0u;
+  h->mut_route = fused ? 1 : 2;
+  rc = sweep_begin(h);
+  if (rc) return rc;
+  const size_t per = (size_t)mut_rows_per_seq(A, L);
+  const bool slabbed_fe = !fused && h->big && slab_fe_on(h);
+  // bytes per row: the outputs; on the general path also the row's expanded rows, their free energies (per sequence
+  // and per motif) and, where the free energies run slab by slab, that pass's scratch (slab_launch_fe)
+  size_t row_bytes = (dfe ? (size_t)L * A * sizeof(float) : 0) + sizeof(float);
+  if (!fused) {
+    row_bytes += per * ((size_t)LW * sizeof(uint32_t) + ((size_t)K + 1) * sizeof(float));
+    if (slabbed_fe) row_bytes += per * (size_t)h->slab->K * h->slab_n * sizeof(float);
+  }
+  int slab = sweep_slab(src, row_bytes);
+  if (!fused) slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)slab, ((size_t)1 << 30) / per));   // expanded rows are counted in int
+  // slabs of equal size: the two streams' launches run side by side, a short last slab would leave one of them idle
+  if (slab < n) slab = (n + (n + slab - 1) / slab - 1) / ((n + slab - 1) / slab);
+  const int nsets = slab < n ? 2 : 1;
+  for (int i = 0; i < nsets; ++i) {        // everything both streams write, at its size, before either starts
+    const SweepSet set = sweep_set(h, i);
+    HIPCHK(h->mut_pll[i].ensure((size_t)slab));
+    if (dfe) HIPCHK(h->mut_df[i].ensure((size_t)slab * L * A));
+    if (!fused) {
+      HIPCHK(h->mut_rows[i].ensure((size_t)slab * per * LW));
+      HIPCHK(set.oa->ensure((size_t)slab * per));
+      HIPCHK(set.ob->ensure((size_t)slab * per * K));
+      if (slabbed_fe) HIPCHK(set.fe_scratch->ensure((size_t)slab * per * h->slab->K * h->slab_n));
+    }
+  }
+  auto launch = [&](int i, const uint32_t* rows, int cnt) -> int {
+    const SweepSet set = sweep_set(h, i & 1);
+    float* d_df = dfe ? h->mut_df[i & 1].p : nullptr;
+    float* d_pll = h->mut_pll[i & 1].p;
+    if (fused) {
+      MutArgs a;
+      a.tables = h->d_tables; a.letters = rows;
+      a.n = cnt; a.L = L; a.Lh = L - h->M + 1; a.LW = LW;
+      a.dfe = d_df; a.pll = d_pll;
+      // num_cu * 8 blocks like the other sweep kernels; a grid of only the resident blocks (5 per CU at config #2: no
+      // second table copy) measured no faster, 8.70 against 8.46 ms over 10^5 x 200 bp: the kernel is bound by its VALU work
+      const unsigned gx = (unsigned)std::max(1, std::min((cnt + waves - 1) / waves, h->num_cu * 8));
+      HIPCHK(jit_launch(h->jk.mutagenesis, a, gx, 1, 64u * (unsigned)waves, lds, set.st));
+      return CRBM_OK;
+    }
+    const size_t R = (size_t)cnt * per;
+    MutExpandArgs e;
+    e.rows = rows; e.out = h->mut_rows[i & 1].p;
+    e.n = cnt; e.L = L; e.LW = LW; e.A = A;
+    hipLaunchKernelGGL(mutagenesis_expand_kernel, dim3(grid_for((long)(R * LW), 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
+    HIPCHK(hipGetLastError());
+    int r = launch_free_energy(h, e.out, (int)R, L, set);
+    if (r) return r;
+    MutCombineArgs c;
+    c.fem = set.ob->p; c.c = h->dc; c.rows = rows;
+    c.n = cnt; c.L = L; c.LW = LW; c.A = A; c.K = K;
+    c.dfe = d_df; c.pll = d_pll;
+    hipLaunchKernelGGL(mutagenesis_combine_kernel, dim3(std::max(1, std::min((cnt + 3) / 4, h->num_cu * 8))), dim3(256), 0, set.st, c);
+    HIPCHK(hipGetLastError());
+    return CRBM_OK;
+  };
+  int prev_i = -1, prev_start = 0, prev_cnt = 0;
+  auto collect = [&]() -> int {     // outputs of the previous slab -> host
+    if (prev_i < 0) return CRBM_OK;
+    const SweepSet set = sweep_set(h, prev_i & 1);
+    if (dfe) HIPCHK(hipMemcpyAsync(dfe + (size_t)prev_start * L * A, h->mut_df[prev_i & 1].p, (size_t)prev_cnt * L * A * sizeof(float), hipMemcpyDeviceToHost, set.st));
+    if (pll) HIPCHK(hipMemcpyAsync(pll + prev_start, h->mut_pll[prev_i & 1].p, (size_t)prev_cnt * sizeof(float), hipMemcpyDeviceToHost, set.st));
+    HIPCHK(hipStreamSynchronize(set.st));
+    return CRBM_OK;
+  };
+  for (int start = 0, i = 0; start < n; start += slab, ++i) {
+    const int cnt = std::min(slab, n - start);
+    const SweepSet set = sweep_set(h, i);
+    const uint32_t* rows = nullptr;
+    rc = sweep_rows(h, src, start, cnt, set, &rows);
+    if (rc) return rc;
+    rc = launch(i, rows, cnt);
+    if (rc) return rc;
+    rc = collect();
+    if (rc) return rc;
+    prev_i = i; prev_start = start; prev_cnt = cnt;
+  }
+  rc = collect();
+  if (rc) return rc;
+  return sweep_finish(h, src);
+}
+
 static RowSource host_onehot_(const float* v, int n, int L, int A) { RowSource s; s.onehot = v; s.n = n; s.L = L; s.A = A; return s; }
 static RowSource host_codes_(const uint8_t* c, int n, int L, int A) { RowSource s; s.codes = c; s.n = n; s.L = L; s.A = A; return s; }
 #define host_onehot(v, n, L) host_onehot_(v, n, L, h->A)
@@ -2894,6 +3004,26 @@ int crbm_motif_sites_resident(crbm_handle* h, int32_t start, int32_t end, float 
   int rc = resident_source(h, start, end, &src);
   if (rc) return rc;
   return motif_sites_any(h, src, threshold, capacity, sites, count, best_start, best_strand, best_prob);
+}
+
+int crbm_mutagenesis(crbm_handle* h, const float* v, int32_t n, int32_t L, float* dfe, float* pll) {
+  ENTER();
+  ARGCHK(v, "null argument");
+  return mutagenesis_any(h, host_onehot(v, n, L), dfe, pll);
+}
+
+int crbm_mutagenesis_codes(crbm_handle* h, const uint8_t* codes, int32_t n, int32_t L, float* dfe, float* pll) {
+  ENTER();
+  ARGCHK(codes, "null argument");
+  return mutagenesis_any(h, host_codes(codes, n, L), dfe, pll);
+}
+
+int crbm_mutagenesis_resident(crbm_handle* h, int32_t start, int32_t end, float* dfe, float* pll) {
+  ENTER();
+  RowSource src;
+  int rc = resident_source(h, start, end, &src);
+  if (rc) return rc;
+  return mutagenesis_any(h, src, dfe, pll);
 }
 
 int crbm_eval_params(crbm_handle* h, float* twn, float* ic, float* medic) {
@@ -3116,6 +3246,7 @@ int crbm_get_launch_info(const crbm_handle* h, crbm_launch_info* out) {
     *out = crbm_launch_info();
     out->gibbs_sparse = 1; out->chain_parts = 1; out->gibbs_block = 256;
     out->activity_ppm = h->activity < 0.0 ? -1 : (int32_t)(h->activity * 1e6 + 0.5);
+    out->mutagenesis_route = h->mut_route;
     return CRBM_OK;
   }
   // the data-half statistics kernel at the chains' shape (stats_mfma_body)
@@ -3138,6 +3269,7 @@ int crbm_get_launch_info(const crbm_handle* h, crbm_launch_info* out) {
   out->stats_fused = h->fuse_stats ? 1 : 0;
   out->gibbs_sparse = h->variant;
   out->activity_ppm = h->activity < 0.0 ? -1 : (int32_t)(h->activity * 1e6 + 0.5);
+  out->mutagenesis_route = h->mut_route;
   return CRBM_OK;
 }
 

@@ -2247,6 +2247,136 @@ __device__ void motif_sites_body(const SitesArgs& a) {
   }
 }
 
+// ===========================================================================
+// In-silico mutagenesis (crbm_mutagenesis*): dF[n,p,a] = F(v_n with letter p replaced by a) - F(v_n), F the
+// unnormalised free energy L * freeEnergy (convRBM.py:657-676), and the pseudo-log-likelihood
+// pll[n] = sum_p -log sum_a exp(-dF[n,p,a]) = sum_p log P(v_p | v_-p).  A substitution at p changes the M windows
+// s in [p-M+1, p] and the visible bias; everything else cancels.  This is the fused pass of the specialised models
+// with POOL == 1: one wave per sequence; a lane owns hidden position s of a 64-position chunk, gathers its activations
+// once per strand and motif-quad group, and for every offset m < M and every x in {1,2,3} forms the activations of the
+// window with letter s+m replaced by (letter ^ x) from ONE other table row, T[g][r ^ (x << 2t)] - T[g][r] (g, t: the
+// group and slot of the letter in this strand's window; the reverse-complemented window holds the complement at the
+// mirrored offset, and complementing commutes with ^ x: the same x names the same forward letter on both strands).
+// The differences go into the wave's accumulator in LDS, acc[x-1][p]: in one step the lanes hold distinct s, hence
+// distinct p = s + m, at consecutive addresses (ds_read_b32 / ds_write_b32: no bank conflict), and the steps follow
+// each other in a fixed order -- no atomics, the same bits in every run.  Indexing by x instead of by the letter
+// keeps the plane wave-uniform; the epilogue turns x into the letter.
+// ===========================================================================
+struct MutArgs {
+  const float* tables;
+  const uint32_t* letters;
+  int32_t n, L, Lh, LW;
+  float* dfe;   // (n, L, 4), or null
+  float* pll;   // (n), or null
+};
+
+// running form of -log sum_a exp(-d_a), overflow-free: mn = the smallest d so far, s = sum exp(-(d - mn))
+__device__ __forceinline__ void pll_push(float d, float& mn, float& s) {
+  if (d < mn) {
+    s = s * __builtin_amdgcn_exp2f(LOG2E * (d - mn)) + 1.0f;
+    mn = d;
+  } else {
+    s += __builtin_amdgcn_exp2f(LOG2E * (mn - d));
+  }
+}
+__device__ __forceinline__ float pll_term(float mn, float s) { return mn - LN2 * __builtin_amdgcn_logf(s); }
+
+template <class C>
+__device__ void mutagenesis_body(const MutArgs& a) {
+  if constexpr (C::POOL == 1) {       // pooled models take the general path (crbm_api.hip): no body
+    constexpr int K = C::K, M = C::M, G = C::G;
+    constexpr int NQW = C::NQ < 4 ? C::NQ : 4, NV = 4 * NQW;
+    HIP_DYNAMIC_SHARED(float, smem);
+    float* Tf = smem;
+    copy_tables<C::TAB>(Tf, a.tables + C::OFF_TF);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const int LP = mut_plane(a.L);
+    float* acc = smem + C::TAB + (size_t)wave * 3 * LP;      // acc[(x - 1) * LP + p]
+    const float* cg = a.tables + C::OFF_C;                   // log2(e) * c
+    const float c0 = LN2 * cg[0], c1 = LN2 * cg[1], c2 = LN2 * cg[2], c3 = LN2 * cg[3];
+    // entry i of four values by its two bits (v_cndmask; an indexed array would live in scratch)
+    auto pick = [](uint32_t i, float v0, float v1, float v2, float v3) {
+      const float lo = (i & 1u) ? v1 : v0, hi = (i & 1u) ? v3 : v2;
+      return (i & 2u) ? hi : lo;
+    };
+    for (int nn = blockIdx.x * nwaves + wave; nn < a.n; nn += gridDim.x * nwaves) {
+      const uint32_t* row = a.letters + (size_t)nn * a.LW;
+      for (int i = lane; i < 3 * LP; i += 64) acc[i] = 0.f;
+      __builtin_amdgcn_wave_barrier();
+      for (int s0 = 0; s0 < a.Lh; s0 += 64) {
+        const int s = s0 + lane;
+        const bool valid = s < a.Lh;
+        const LetterWin<M> fwd = letter_window<M>(row, valid ? s : a.Lh - 1);
+#pragma unroll 1
+        for (int strand = 0; strand <= C::DS; ++strand) {
+          const LetterWin<M> win = strand ? revcomp_window<M>(fwd) : fwd;
+#pragma unroll 1
+          for (int q0 = 0; q0 < C::NQ; q0 += NQW) {
+            float z[NV], sp[NV];
+            conv_gather_quads<C, NQW>(Tf, win, q0, z);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) sp[j] = 4 * q0 + j < K ? softplus_of_z(z[j]) : 0.f;
+#pragma unroll 1
+            for (int m = 0; m < M; ++m) {
+              const int o = strand ? M - 1 - m : m;          // the letter's offset in this strand's window
+              const int g = o / G, t = o - g * G;
+              const uint32_t r = window_bits<M>(win, 2 * G * g) & (uint32_t)(C::ROWS - 1);
+              const float4* tab = reinterpret_cast<const float4*>(Tf + (size_t)g * C::ROWS * C::KP) + q0;
+              float cur[NV];
+#pragma unroll
+              for (int q = 0; q < NQW; ++q)
+                if (q0 + q < C::NQ) {                        // wave-uniform
+                  const float4 v = tab[(size_t)r * C::NQ + q];
+                  cur[4 * q] = v.x; cur[4 * q + 1] = v.y; cur[4 * q + 2] = v.z; cur[4 * q + 3] = v.w;
+                }
+#pragma unroll
+              for (int x = 1; x < 4; ++x) {
+                const uint32_t r2 = r ^ ((uint32_t)x << (2 * t));
+                float d = 0.f;
+#pragma unroll
+                for (int q = 0; q < NQW; ++q)
+                  if (q0 + q < C::NQ) {
+                    const float4 v = tab[(size_t)r2 * C::NQ + q];
+                    const float alt[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                      if (4 * (q0 + q) + e < K) d += softplus_of_z(z[4 * q + e] + (alt[e] - cur[4 * q + e])) - sp[4 * q + e];
+                  }
+                if (valid) acc[(x - 1) * LP + s + m] -= d;   // F carries -softplus
+              }
+              __builtin_amdgcn_wave_barrier();               // the next step's lanes read what this step's neighbours wrote
+            }
+          }
+        }
+      }
+      // x -> letter, the visible bias -(c[a] - c[v_p]), the position's term of the pseudo-log-likelihood
+      float lsum = 0.f;
+      for (int p0 = 0; p0 < a.L; p0 += 64) {
+        const int p = p0 + lane;
+        if (p < a.L) {
+          const uint32_t l = (row[p >> 4] >> (2 * (p & 15))) & 3u;
+          const float cl = pick(l, c0, c1, c2, c3);
+          const float d1 = acc[p] - (pick(l ^ 1u, c0, c1, c2, c3) - cl), d2 = acc[LP + p] - (pick(l ^ 2u, c0, c1, c2, c3) - cl),
+                      d3 = acc[2 * LP + p] - (pick(l ^ 3u, c0, c1, c2, c3) - cl);
+          if (a.dfe) {
+            float4 o4;                                       // letter a holds the difference of x = a ^ l
+            o4.x = pick(l, 0.f, d1, d2, d3); o4.y = pick(l ^ 1u, 0.f, d1, d2, d3);
+            o4.z = pick(l ^ 2u, 0.f, d1, d2, d3); o4.w = pick(l ^ 3u, 0.f, d1, d2, d3);
+            reinterpret_cast<float4*>(a.dfe)[(size_t)nn * a.L + p] = o4;
+          }
+          float mn = 0.f, sm = 1.f;                          // the sequence's own letter: dF = 0
+          pll_push(d1, mn, sm); pll_push(d2, mn, sm); pll_push(d3, mn, sm);
+          lsum += pll_term(mn, sm);
+        }
+      }
+      lsum = wave_sum(lsum);
+      if (lane == 0 && a.pll) a.pll[nn] = lsum;
+      __builtin_amdgcn_wave_barrier();                       // the accumulator is cleared for the wave's next sequence
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Normalise the (all-reduced) raw sums and apply the SGD+momentum update
 // (convRBM.py:358-371, :415-436, :440-451).

@@ -849,3 +849,91 @@ __global__ void __launch_bounds__(256) slab_fe_combine_kernel(SlabFeCombineArgs 
     if (lane == 0 && a.fe) a.fe[nn] = (tot - cs) / (float)a.L;
   }
 }
+
+// ---- in-silico mutagenesis, general path (crbm_api.hip, mutagenesis_any: pooled models, slab models, motifs beyond 64
+// letters, other alphabets; crbm_kernels.h, mutagenesis_body, has the definitions) -----------------------------------
+// Expand: for every base row its (A-1) L single-substitution copies in the packed layout the free-energy pass reads.
+// Output row i (1 + (A-1) L) is base row i itself, row i (1 + (A-1) L) + 1 + p (A-1) + (x-1) has letter p replaced by
+// (letter + x) mod A, x = 1 .. A-1.  One thread per output word.
+struct MutExpandArgs {
+  const uint32_t* rows;
+  uint32_t* out;
+  int32_t n, L, LW, A;
+};
+__host__ __device__ __forceinline__ long long mut_rows_per_seq(int A, int L) { return 1 + (long long)(A - 1) * L; }
+
+__global__ void __launch_bounds__(256) mutagenesis_expand_kernel(MutExpandArgs a) {
+  const long long per = mut_rows_per_seq(a.A, a.L);
+  const size_t words = (size_t)a.n * (size_t)per * (size_t)a.LW;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t orow = i / (size_t)a.LW;
+    const int w = (int)(i - orow * (size_t)a.LW);
+    const size_t nn = orow / (size_t)per;
+    const int j = (int)(orow - nn * (size_t)per);
+    uint32_t v = a.rows[nn * (size_t)a.LW + w];
+    if (j > 0) {
+      const int p = (j - 1) / (a.A - 1), x = 1 + (j - 1) - p * (a.A - 1);
+      if (a.A == 4) {
+        if ((p >> 4) == w) {
+          const int sh = 2 * (p & 15);
+          const uint32_t l = (v >> sh) & 3u;
+          v = (v & ~(3u << sh)) | (((l + (uint32_t)x) & 3u) << sh);
+        }
+      } else if ((p >> 2) == w) {
+        const int sh = 8 * (p & 3);
+        const uint32_t l = (v >> sh) & 0xffu;
+        v = (v & ~(0xffu << sh)) | (((l + (uint32_t)x) % (uint32_t)a.A) << sh);
+      }
+    }
+    a.out[i] = v;
+  }
+}
+
+// Combine: the per-motif free energies fem[row][k] = -v_k - cs of the expanded rows (free_energy_body's `fem`, from any
+// of the free-energy routes) -> dF and pll.  The difference is taken PER MOTIF and then summed over the motifs in their
+// order, sum_k ((fem'_k - fem_k) + dc) - dc with dc = c[a] - c[v_p] from c itself (cs' - cs = dc up to the rounding of
+// two long sums: added back per motif, it leaves -(v'_k - v_k)): the difference of the two totals would carry the
+// rounding of sums over all motifs.  One wave per sequence, a lane per position, every sum in a fixed order.
+struct MutCombineArgs {
+  const float* fem;          // (n (1 + (A-1) L), K)
+  const float* c;            // (A)
+  const uint32_t* rows;      // the n base rows
+  int32_t n, L, LW, A, K;
+  float* dfe;                // (n, L, A), or null
+  float* pll;                // (n), or null
+};
+
+__global__ void __launch_bounds__(256) mutagenesis_combine_kernel(MutCombineArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const long long per = mut_rows_per_seq(a.A, a.L);
+  BigModel bm;
+  bm.W = nullptr; bm.b = nullptr; bm.c = a.c; bm.K = a.K; bm.M = 0; bm.ds = 0; bm.NW = 0; bm.A = a.A;
+  for (int nn = blockIdx.x * nwaves + wave; nn < a.n; nn += gridDim.x * nwaves) {
+    const uint32_t* row = a.rows + (size_t)nn * a.LW;
+    const float* f0 = a.fem + (size_t)nn * (size_t)per * a.K;
+    float lsum = 0.f;
+    for (int p0 = 0; p0 < a.L; p0 += 64) {
+      const int p = p0 + lane;
+      if (p < a.L) {
+        const uint32_t l = letter_at(bm, row, p);
+        const float cl = a.c[l];
+        float* out = a.dfe ? a.dfe + ((size_t)nn * a.L + p) * a.A : nullptr;
+        if (out) out[l] = 0.f;
+        float mn = 0.f, sm = 1.f;                 // the sequence's own letter: dF = 0
+        for (int x = 1; x < a.A; ++x) {
+          const uint32_t l2 = (l + (uint32_t)x) % (uint32_t)a.A;
+          const float dc = a.c[l2] - cl;
+          const float* f1 = f0 + ((size_t)1 + (size_t)p * (a.A - 1) + (x - 1)) * a.K;
+          float d = 0.f;
+          for (int k = 0; k < a.K; ++k) d += (f1[k] - f0[k]) + dc;
+          d -= dc;
+          if (out) out[l2] = d;
+          pll_push(d, mn, sm);
+        }
+        lsum += pll_term(mn, sm);
+      }
+    }
+    lsum = wave_sum(lsum);
+    if (lane == 0 && a.pll) a.pll[nn] = lsum;
+  }
+}

@@ -41,6 +41,8 @@ inline int letter_words(int L) { return (L + 15) / 16 + 2; }
 // Alphabets of A != 4 letters (input_dims, convRBM.py:68; generic kernels only): one byte per letter, four per word,
 // the same two pad words.
 inline int letter_words_any(int A, int L) { return A == 4 ? letter_words(L) : (L + 3) / 4 + 2; }
+// Mutagenesis kernel (crbm_kernels.h, mutagenesis_body): floats per plane of a wave's LDS accumulator, three planes per wave
+constexpr int mut_plane(int L) { return (L + 63) & ~63; }
 // Largest motif length the letter windows hold (two 64-bit words); the number of motifs is
 // bounded by what the LDS holds (tables + one chain: choose_gibbs_geometry refuses beyond)
 // and by the statistics kernel (one role of 64 threads per 16 motifs, at most 1024 threads per block).

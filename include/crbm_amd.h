@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CRBM_AMD_ABI_VERSION 4
+#define CRBM_AMD_ABI_VERSION 5
 
 typedef enum crbm_status {
   CRBM_OK = 0,
@@ -225,6 +225,23 @@ int crbm_motif_sites_resident(crbm_handle* h, int32_t start, int32_t end, float 
                               crbm_site* sites, int64_t* count, int32_t* best_start, int32_t* best_strand,
                               float* best_prob);
 
+/* ---- in-silico mutagenesis and pseudo-log-likelihood -----------------------------
+ * WHICH bases matter.  With F(v) = L * crbm_free_energy(v), the unnormalised free energy of one sequence (derived from
+ * theano_freeEnergyForData, convRBM.py:657-676: the hidden terms of all motifs and strands, pooled form when
+ * pooling > 1, minus the visible bias term):
+ *   dfe[n,p,a] = F(v_n with letter p replaced by a) - F(v_n)           (n,L,input_dims) fp32
+ *   pll[n]     = sum_p -log sum_a exp(-dfe[n,p,a]) = sum_p log P(v_p | v_-p)      (n) fp32, <= 0
+ * dfe[n,p,v_n[p]] is exactly 0; negative: the substitution fits the model better.  Only the motif_length windows
+ * that cover p and the visible bias are evaluated (convRBM.py:657-676 restricted to what a substitution changes);
+ * the mutated sequences never exist for specialised models without pooling (one fused kernel), every other model
+ * expands a chunk of rows into its single-substitution copies on the device and runs its free-energy pass over them
+ * (CRBM_MUT_FUSED=0 forces that path).  Either output may be NULL (pll alone never holds n*L*input_dims anywhere),
+ * both NULL is CRBM_ERR_INVALID, and so is L < motif_length.  The same bits in every run, for every input form and
+ * every CRBM_SLAB_BYTES. */
+int crbm_mutagenesis(crbm_handle* h, const float* v, int32_t n, int32_t L, float* dfe, float* pll);
+int crbm_mutagenesis_codes(crbm_handle* h, const uint8_t* codes, int32_t n, int32_t L, float* dfe, float* pll);
+int crbm_mutagenesis_resident(crbm_handle* h, int32_t start, int32_t end, float* dfe, float* pll);
+
 /* ---- data-parallel (new: the reference is single-device) -----------------
  * One process per GPU.  Rank 0 calls crbm_comm_unique_id and distributes the
  * 128 bytes by any host channel; every rank then calls crbm_comm_init.  After
@@ -285,6 +302,7 @@ typedef struct crbm_launch_info {
   int32_t stats_fused;   /* 1: the model half of the gradient statistics rides in the Gibbs launch of a training step */
   int32_t chain_parts;   /* plain chain launches (crbm_gibbs_steps*) go out as this many launches of a share of the chains
                             each, on streams of their own (the gibbs_* fields above then describe ONE of them)          */
+  int32_t mutagenesis_route;  /* route of the last crbm_mutagenesis* call: 1 = fused kernel, 2 = general path, 0 = none yet */
 } crbm_launch_info;
 int crbm_get_launch_info(const crbm_handle* h, crbm_launch_info* out);
 /* Device-copy bandwidth (float4 copy kernel, HIP events, read + written bytes
