@@ -121,6 +121,7 @@ SIGNATURES = {
     "crbm_mutagenesis": (_I32, [_H, _F, _I32, _I32, _F, _F]),
     "crbm_mutagenesis_codes": (_I32, [_H, _U8P, _I32, _I32, _F, _F]),
     "crbm_mutagenesis_resident": (_I32, [_H, _I32, _I32, _F, _F]),
+    "crbm_ais": (_I32, [_H, _I32, _I32, _U32, _F, _I32, _I32, _I32, _F, _U64, _U8P, _F]),
     "crbm_comm_unique_id": (_I32, [_U8P]),
     "crbm_comm_init": (_I32, [_H, _U8P, _I32, _I32]),
     "crbm_comm_destroy": (_I32, [_H]),

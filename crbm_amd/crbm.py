@@ -526,6 +526,95 @@ class CRBM(object):
             self._call("crbm_free_energy_per_motif" if permotif else "crbm_free_energy", *(args + (fptr(out),)))
         return out
 
+    # ------------------------------------------- annealed importance sampling
+    @staticmethod
+    def _ais_ladder(betas):
+        """The ladder as float32: an int T (linspace(0, 1, T + 1)) or an array from 0 to 1 that never decreases."""
+        if isinstance(betas, (int, np.integer)) and not isinstance(betas, bool):
+            if betas < 1:
+                raise ValueError("betas must be at least 1 temperature step, got %r" % (betas,))
+            return np.linspace(0.0, 1.0, int(betas) + 1).astype(np.float32)
+        b = np.ascontiguousarray(betas, dtype=np.float32)
+        if b.ndim != 1 or b.size < 2:
+            raise ValueError("betas must be an int or a 1-D array of at least two values")
+        if not np.all(np.isfinite(b)) or b[0] != 0.0 or b[-1] != 1.0:
+            raise ValueError("betas must start at 0 and end at 1")
+        if np.any(np.diff(b) < 0):
+            raise ValueError("betas must not decrease")
+        return b
+
+    def _ais_base(self, base):
+        """cA (A,) float32 of the base-rate model, or None for the model's own c.  `base`: None, a (1,A) / (A,) array
+        of biases, or data (letter codes or one-hot) whose letter frequencies with a pseudo-count of 1 give cA."""
+        A = self.input_dims
+        if base is None:
+            return None
+        if self._is_codes(base):
+            if base.size and base.max() >= A:
+                raise ValueError("base holds a letter code outside 0..%d" % (A - 1))
+            counts = np.bincount(base.ravel(), minlength=A).astype(np.float64)
+        else:
+            arr = np.asarray(base)
+            if arr.ndim == 4 and arr.shape[1] == 1 and arr.shape[2] == A:
+                counts = arr.astype(np.float64).sum(axis=(0, 1, 3))
+            elif arr.shape in ((A,), (1, A)) and np.issubdtype(arr.dtype, np.number):
+                cA = np.ascontiguousarray(arr.reshape(A), dtype=np.float32)
+                if not np.all(np.isfinite(cA)):
+                    raise ValueError("base must be finite")
+                return cA
+            else:
+                raise ValueError("base must be None, a (1,%d) or (%d,) array of biases, (n,L) uint8 codes or one-hot "
+                                 "data (n,1,%d,L); got shape %s" % (A, A, A, arr.shape))
+        freq = (counts + 1.0) / (counts.sum() + A)
+        return np.log(freq).astype(np.float32)
+
+    def logPartition(self, L, runs=4096, betas=1000, base=None, seed=None, return_runs=False):
+        """log Z of the model for sequences of length L by annealed importance sampling (Salakhutdinov & Murray
+        2008): `runs` independent runs from a base-rate model (independent letters with bias cA, `base`) to the
+        model over the ladder `betas` of inverse temperatures.  Returns dict(logZ, stderr, ess, logZ_base):
+        logZ = logZ_base + log mean exp(logw), stderr its standard error by the delta method
+        (std(w) / (mean(w) sqrt(runs))), ess = (sum w)^2 / sum w^2 the effective number of runs, logZ_base the exact
+        log partition function of the base-rate model; with return_runs also logw (runs,) float32.
+        `betas`: an int T (T equal steps) or an array from 0 to 1; `base`: None (the model's c), a (1,A) / (A,) array,
+        or data whose letter frequencies give cA; `seed`: None takes the model's.  Z belongs to a length: the model
+        is convolutional.  DNA models on the specialised kernels without pooling."""
+        L, runs = int(L), int(runs)
+        if runs < 1:
+            raise ValueError("runs must be at least 1, got %d" % runs)
+        if L < self.motif_length:
+            raise ValueError("sequences of length %d are shorter than motif_length %d" % (L, self.motif_length))
+        ladder = self._ais_ladder(betas)
+        cA = self._ais_base(base)
+        seed = self.seed if seed is None else int(seed)
+        logw = np.empty(runs, dtype=np.float32)
+        self._call("crbm_ais", L, runs, 0, fptr(ladder), ladder.size, 0, ladder.size - 1, fptr(cA),
+                   seed & 0xFFFFFFFFFFFFFFFF, None, fptr(logw))
+        base_c = (self.c.get_value().reshape(-1) if cA is None else cA).astype(np.float64)
+        S = 2 if self.doublestranded else 1
+        mx = base_c.max()
+        logz_base = L * (mx + np.log(np.exp(base_c - mx).sum())) + S * self.num_motifs * (L - self.motif_length + 1) * np.log(2.0)
+        lw = logw.astype(np.float64)
+        w = np.exp(lw - lw.max())
+        out = {"logZ": float(logz_base + lw.max() + np.log(w.mean())),
+               "stderr": float(w.std() / (w.mean() * np.sqrt(runs))),
+               "ess": float(w.sum() ** 2 / (w * w).sum()),
+               "logZ_base": float(logz_base)}
+        if return_runs:
+            out["logw"] = logw
+        return out
+
+    def logLikelihood(self, data, logZ=None, **ais):
+        """(n,) float32: the normalised log-likelihood of every sequence, -L * freeEnergy(v) - logZ.  `logZ`: that of
+        logPartition(L) for the data's length L; None computes it (keyword arguments go to logPartition).
+        `data`: one-hot or (n, L) uint8 codes."""
+        suffix, args, n, L, _keep = self._sites_input(data)
+        if logZ is None:
+            logZ = self.logPartition(L, **ais)["logZ"]
+        elif ais:
+            raise TypeError("logZ is given: unexpected keyword arguments %s" % sorted(ais))
+        fe = self.freeEnergy(data).astype(np.float64)
+        return (-L * fe - float(logZ)).astype(np.float32)
+
     def getPFMs(self):
         """Position frequency matrices of the filters: per motif a (4,M) float64 array whose
         columns are the softmax of the filter column over the four letters (what

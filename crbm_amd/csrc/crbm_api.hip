@@ -175,6 +175,9 @@ struct crbm_handle {
   DevBuf<float> mut_df[2], mut_pll[2];
   DevBuf<uint32_t> mut_rows[2];
   int mut_route = 0;                               // route of the last crbm_mutagenesis* call: 1 fused kernel, 2 general path
+  // annealed importance sampling (crbm_ais): the ladder, cA, the runs' log weights and letter codes between launches
+  DevBuf<float> ais_betas, ais_base, ais_logw;
+  DevBuf<uint8_t> ais_state;
   float* d_sums = nullptr;
   int dataset_n[CRBM_DATASET_SLOTS] = {0, 0}, dataset_L[CRBM_DATASET_SLOTS] = {0, 0};
   int slot = 0;
@@ -1778,6 +1781,7 @@ int crbm_destroy(crbm_handle* h) {
   for (auto& d : h->dataset) d.release(); h->partials.release(); h->partials2.release();
   for (int i = 0; i < 2; ++i) { h->site_recs[i].release(); h->site_count[i].release(); h->site_keys[i].release(); }
   for (int i = 0; i < 2; ++i) { h->mut_df[i].release(); h->mut_pll[i].release(); h->mut_rows[i].release(); }
+  h->ais_betas.release(); h->ais_base.release(); h->ais_logw.release(); h->ais_state.release();
   if (h->jk.module) (void)hipModuleUnload(h->jk.module);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -3024,6 +3028,71 @@ int crbm_mutagenesis_resident(crbm_handle* h, int32_t start, int32_t end, float*
   int rc = resident_source(h, start, end, &src);
   if (rc) return rc;
   return mutagenesis_any(h, src, dfe, pll);
+}
+
+// Steps [t0,t1) of an annealed-importance-sampling ladder (include/crbm_amd.h; kernel: ais_body).  One wave per run, as
+// many waves per block (at most four) as the LDS holds run slices beside the tables; the ladder goes out in launches of
+// at most CRBM_AIS_STEPS steps (default 64: one launch then takes 2.0 ms for 8192 runs of 200 bp on config #2's model and 13.5 ms for 1024 runs of
+// 1000 bp on config #4's, profiles/ais_bench.json), the letters and the float32 log weights of the runs
+// passing from launch to launch in the handle's own buffers.
+int crbm_ais(crbm_handle* h, int32_t L, int32_t runs, uint32_t run_offset, const float* betas, int32_t nbetas,
+             int32_t t0, int32_t t1, const float* base_c, uint64_t seed, uint8_t* state, float* logw) {
+  ENTER();
+  ARGCHK(h->ms.POOL == 1, "crbm_ais: pooling > 1 is not supported (the pooled sampler and the pooled free energy normalise differently)");
+  ARGCHK(h->A == 4, "crbm_ais: alphabets other than DNA's (input_dims != 4) are not supported");
+  ARGCHK(!h->big, "crbm_ais: models on the generic kernels are not supported");
+  ARGCHK(betas && logw, "null argument");
+  ARGCHK(L >= h->M, "sequence length must be >= motif_length");
+  ARGCHK((long)L * 4 < (1 << 20), "sequence too long");
+  ARGCHK(runs > 0, "runs must be positive");
+  ARGCHK(nbetas >= 2, "nbetas must be at least 2");
+  ARGCHK(0 <= t0 && t0 < t1 && t1 <= nbetas - 1, "t0, t1 must satisfy 0 <= t0 < t1 <= nbetas - 1");
+  for (int i = 0; i < nbetas; ++i) {
+    ARGCHK(std::isfinite(betas[i]), "betas must be finite");
+    ARGCHK(betas[i] >= 0.f && betas[i] <= 1.f, "betas must lie inside [0,1]");
+    ARGCHK(i == 0 || betas[i] >= betas[i - 1], "betas must not decrease");
+  }
+  ARGCHK(t0 == 0 || state, "t0 > 0 needs the state of the runs");
+  if (base_c)
+    for (int a = 0; a < 4; ++a) ARGCHK(std::isfinite(base_c[a]), "base_c must be finite");
+  const AisLayout al = ais_layout(h->ms, L);
+  int waves = 4;
+  while (waves >= 1 && ais_lds_bytes(h->ms, al, waves) > 160L * 1024L) waves >>= 1;
+  ARGCHK(waves >= 1, "crbm_ais: a run of this length does not fit the LDS beside the model's tables");
+  const size_t nstate = (size_t)runs * L;
+  if (t0 > 0)
+    for (size_t i = 0; i < nstate; ++i) ARGCHK(state[i] < 4, "state holds a letter code outside 0..3");
+  const int max_steps = std::max(1, env_int("CRBM_AIS_STEPS", 64));
+  int rc = ensure_tables(h);
+  if (rc) return rc;
+  HIPCHK(h->ais_betas.ensure((size_t)nbetas));
+  HIPCHK(h->ais_base.ensure(4));
+  HIPCHK(h->ais_logw.ensure((size_t)runs));
+  HIPCHK(h->ais_state.ensure(nstate));
+  HIPCHK(hipMemcpyAsync(h->ais_betas.p, betas, (size_t)nbetas * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (base_c) HIPCHK(hipMemcpyAsync(h->ais_base.p, base_c, 4 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  else HIPCHK(hipMemcpyAsync(h->ais_base.p, h->dc, 4 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  if (t0 > 0) {
+    HIPCHK(hipMemcpyAsync(h->ais_state.p, state, nstate, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->ais_logw.p, logw, (size_t)runs * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  }
+  AisArgs a;
+  a.tables = h->d_tables; a.base_c = h->ais_base.p; a.betas = h->ais_betas.p;
+  a.state = h->ais_state.p; a.logw = h->ais_logw.p;
+  a.runs = runs; a.L = L; a.Lh = L - h->M + 1;
+  a.nvb = al.nvb; a.Lrow = al.Lrow; a.LWs = al.LWs; a.run_words = al.run_words;
+  a.rng.seed_lo = (uint32_t)(seed & 0xffffffffu); a.rng.seed_hi = (uint32_t)(seed >> 32);
+  a.rng.step = 0; a.rng.seq_offset = run_offset;
+  const unsigned gx = (unsigned)std::max(1, std::min((runs + waves - 1) / waves, h->num_cu * 8));
+  const unsigned lds = (unsigned)ais_lds_bytes(h->ms, al, waves);
+  for (int t = t0; t < t1; t += max_steps) {
+    a.t0 = t; a.t1 = std::min(t1, t + max_steps);
+    HIPCHK(jit_launch(h->jk.ais, a, gx, 1, 64u * (unsigned)waves, lds, h->stream));
+  }
+  HIPCHK(hipMemcpyAsync(logw, h->ais_logw.p, (size_t)runs * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (state) HIPCHK(hipMemcpyAsync(state, h->ais_state.p, nstate, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return CRBM_OK;
 }
 
 int crbm_eval_params(crbm_handle* h, float* twn, float* ic, float* medic) {

@@ -2377,6 +2377,174 @@ __device__ void mutagenesis_body(const MutArgs& a) {
   }
 }
 
+// ===========================================================================
+// Annealed importance sampling (Neal 2001; Salakhutdinov & Murray 2008): steps [t0, t1) of the ladder betas[] for
+// `runs` independent runs, POOL == 1.  With x, x' the bottom-up activations of the two strands,
+//   log p*_beta(v) = sum softplus(beta x(v)) + sum_p (beta c[v_p] + (1 - beta) cA[v_p]),
+// step t adds log p*_{betas[t+1]}(v_t) - log p*_{betas[t]}(v_t) to the run's log weight and then takes one Gibbs step
+// of the model tempered to betas[t+1]: h ~ sigma(beta x(v_t)), v_{t+1} ~ softmax(beta (c + W^T h + ..) + (1 - beta) cA).
+// One wave owns a run; its letter row and mask rows stay in the LDS for all steps of the launch (AisLayout), so
+// nothing but wave barriers separates the passes.  The tables are the chain kernel's (built for beta = 1): the
+// gathered z = -log2(e) x is multiplied by beta, the top-down image (in units of log 2) enters through one fma per
+// letter.  The two softplus terms of a unit share its gather and are differenced per unit; a lane adds its units in
+// program order, the wave total comes from wave_sum and is added to the float32 log weight once per step -- the bits
+// depend on nothing but (run, ladder), not on the launch geometry or on where the ladder is cut into launches (what
+// crosses a cut is the letters and the float32 log weight, nothing else).
+// Uniforms: kinds KIND_AIS_V / KIND_AIS_H with the chain's counter layout, sequence word run_offset + run, step word
+// 0 for the base-rate draw and t + 1 for step t.
+// ===========================================================================
+struct AisArgs {
+  const float* tables;
+  const float* base_c;   // (4) visible bias cA of the base-rate model
+  const float* betas;    // the ladder
+  uint8_t* state;        // (runs, L) letter codes: read when t0 > 0, written at the end; may be null when t0 == 0
+  float* logw;           // (runs): read when t0 > 0, written at the end
+  int32_t runs, L, Lh, t0, t1;
+  int32_t nvb, Lrow, LWs, run_words;   // AisLayout
+  RngView rng;           // seed of the call; seq_offset = global index of run 0
+};
+
+template <class C>
+__device__ void ais_body(const AisArgs& a) {
+  if constexpr (C::POOL == 1) {       // crbm_ais refuses pooled models: no body
+    constexpr int K = C::K, KP = C::KP, M = C::M, NW = C::NW;
+    HIP_DYNAMIC_SHARED(float, smem);
+    copy_tables<C::TAB>(smem, a.tables + C::OFF_TF);
+    copy_tables<C::WS * (1 + C::DS) + 4>(smem + C::SP_WS, a.tables + C::OFF_WS);
+    __syncthreads();
+    const float* Tf = smem;
+    const float* cv = smem + C::SP_C;                       // log2(e) * c
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const int rowW = a.Lrow * NW;
+    uint32_t* hm = reinterpret_cast<uint32_t*>(smem + C::SP_TABLES) + (size_t)wave * a.run_words;
+    uint32_t* hmp = hm + rowW;
+    uint32_t* let = hm + (1 + C::DS) * rowW;
+    const float m0 = cv[0], m1 = cv[1], m2 = cv[2], m3 = cv[3];
+    // the base-rate bias in the units of the top-down images, and c - cA per letter (exactly 0 where cA is c)
+    const float a0 = LOG2E * a.base_c[0], a1 = LOG2E * a.base_c[1], a2 = LOG2E * a.base_c[2], a3 = LOG2E * a.base_c[3];
+    const float d0 = LN2 * (m0 - a0), d1 = LN2 * (m1 - a1), d2 = LN2 * (m2 - a2), d3 = LN2 * (m3 - a3);
+    auto pick = [](uint32_t i, float v0, float v1, float v2, float v3) {
+      const float lo = (i & 1u) ? v1 : v0, hi = (i & 1u) ? v3 : v2;
+      return (i & 2u) ? hi : lo;
+    };
+    for (int run = blockIdx.x * nwaves + wave; run < a.runs; run += gridDim.x * nwaves) {
+      const uint32_t gn = a.rng.seq_offset + (uint32_t)run;
+      for (int i = lane; i < a.run_words; i += 64) hm[i] = 0u;   // mask pads and letter pads stay zero
+      __builtin_amdgcn_wave_barrier();
+      float logw = 0.f;
+      if (a.t0 == 0) {
+        // v_0 ~ softmax(cA), four positions per Philox call like every visible draw
+        for (int pb = lane; pb < a.nvb; pb += 64) {
+          const Philox4 r = philox4x32(gn, (uint32_t)pb, rng_word2(KIND_AIS_V, 0, 0, 0), 0u, a.rng.seed_lo, a.rng.seed_hi);
+          uint32_t byte = 0u;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) byte |= (4 * pb + i < a.L ? sample_letter(a0, a1, a2, a3, u01(r.v[i])) : 0u) << (2 * i);
+          reinterpret_cast<unsigned char*>(let)[pb] = (unsigned char)byte;
+        }
+      } else {
+        logw = a.logw[run];
+        const uint8_t* src = a.state + (size_t)run * a.L;
+        for (int pb = lane; pb < a.nvb; pb += 64) {
+          uint32_t byte = 0u;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) byte |= (4 * pb + i < a.L ? (uint32_t)src[4 * pb + i] & 3u : 0u) << (2 * i);
+          reinterpret_cast<unsigned char*>(let)[pb] = (unsigned char)byte;
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+      for (int t = a.t0; t < a.t1; ++t) {
+        const float b0 = a.betas[t], b1 = a.betas[t + 1];
+        // ---- weight of the step and h | v_t at betas[t+1], one hidden position per lane and round ----
+        float acc = 0.f;
+        for (int s = lane; s < a.Lh; s += 64) {
+          const LetterWin<M> win = letter_window<M>(let, s);
+#pragma unroll
+          for (int strand = 0; strand <= C::DS; ++strand) {
+            float z[KP], p[KP];
+            conv_gather<C>(Tf, strand ? revcomp_window<M>(win) : win, z);
+#pragma unroll
+            for (int k = 0; k < KP; ++k) {
+              const float zb = b1 * z[k];
+              if (k < K) acc += softplus_of_z(zb) - softplus_of_z(b0 * z[k]);
+              z[k] = zb;
+            }
+            uint32_t mask[NW];
+            sample_hidden<C, 0>(z, gn, (uint32_t)s, KIND_AIS_H, (uint32_t)strand, a.rng, (uint32_t)(t + 1), mask, p);
+            uint32_t* dst = (strand ? hmp : hm) + (size_t)(s + M - 1) * NW;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) dst[w] = mask[w];
+          }
+        }
+        float vs = 0.f;                                     // sum_p (c - cA)[v_p]
+        for (int p = lane; p < a.L; p += 64) vs += pick((let[p >> 4] >> (2 * (p & 15))) & 3u, d0, d1, d2, d3);
+        acc += (b1 - b0) * vs;
+        logw += wave_sum(acc);
+        __builtin_amdgcn_wave_barrier();                    // every mask of the step is stored
+        // ---- v_{t+1} | h: the set-bit walk of the chain kernel over the run's mask rows ----
+        const float omb = 1.0f - b1;
+        const float e0 = omb * a0, e1 = omb * a1, e2 = omb * a2, e3 = omb * a3;
+        for (int pb = lane; pb < a.nvb; pb += 64) {
+          const int p0 = 4 * pb;
+          float y[4][4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { y[i][0] = m0; y[i][1] = m1; y[i][2] = m2; y[i][3] = m3; }
+          constexpr int NSLOT = M + 3;
+          constexpr int PPW = NW == 1 ? 64 / K : 1;         // masks per 64-bit word
+          constexpr int NWORD = (NSLOT + PPW - 1) / PPW;
+#pragma unroll
+          for (int strand = 0; strand <= C::DS; ++strand) {
+            const uint32_t* mrow = (strand ? hmp : hm) + (size_t)p0 * NW;
+            const char* tab = reinterpret_cast<const char*>(smem + (strand ? C::SP_WSR : C::SP_WS));
+            if constexpr (NW == 1) {
+              constexpr int NMV = (NSLOT + 3) / 4;
+              uint32_t m[4 * NMV];
+#pragma unroll
+              for (int v4 = 0; v4 < NMV; ++v4) {
+                const uint4 mm = reinterpret_cast<const uint4*>(mrow)[v4];
+                m[4 * v4] = mm.x; m[4 * v4 + 1] = mm.y; m[4 * v4 + 2] = mm.z; m[4 * v4 + 3] = mm.w;
+              }
+#pragma unroll
+              for (int wi = 0; wi < NWORD; ++wi) {
+                unsigned long long w = 0ull;
+#pragma unroll
+                for (int q = 0; q < PPW; ++q)
+                  if (wi * PPW + q < NSLOT) w |= (unsigned long long)m[wi * PPW + q] << (q * K);
+                topdown_bits<C>(w, tab, wi * PPW, y);
+              }
+            } else {
+#pragma unroll 1
+              for (int q = 0; q < NSLOT; ++q) {
+#pragma unroll
+                for (int w2 = 0; 2 * w2 < NW; ++w2) {
+                  const uint32_t lo = mrow[NW * q + 2 * w2], hi = 2 * w2 + 1 < NW ? mrow[NW * q + 2 * w2 + 1] : 0u;
+                  topdown_bits<C>((unsigned long long)lo | ((unsigned long long)hi << 32), tab, q, y, 64 * w2);
+                }
+              }
+            }
+          }
+          const Philox4 r = philox4x32(gn, (uint32_t)pb, rng_word2(KIND_AIS_V, 0, 0, 0), (uint32_t)(t + 1), a.rng.seed_lo, a.rng.seed_hi);
+          uint32_t byte = 0u;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const uint32_t l = sample_letter(fmaf(b1, y[i][0], e0), fmaf(b1, y[i][1], e1), fmaf(b1, y[i][2], e2), fmaf(b1, y[i][3], e3),
+                                             u01(r.v[i]));
+            byte |= (p0 + i < a.L ? l : 0u) << (2 * i);
+          }
+          reinterpret_cast<unsigned char*>(let)[pb] = (unsigned char)byte;
+        }
+        __builtin_amdgcn_wave_barrier();                    // the next step gathers from the new letters
+      }
+      if (lane == 0) a.logw[run] = logw;
+      if (a.state) {
+        uint8_t* dst = a.state + (size_t)run * a.L;
+        for (int p = lane; p < a.L; p += 64) dst[p] = (uint8_t)((let[p >> 4] >> (2 * (p & 15))) & 3u);
+      }
+      __builtin_amdgcn_wave_barrier();                      // the slice is cleared for the wave's next run
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Normalise the (all-reduced) raw sums and apply the SGD+momentum update
 // (convRBM.py:358-371, :415-436, :440-451).

@@ -9,7 +9,8 @@ namespace crbm {
 // Philox counter "kind" field (bits 28..31 of counter word 2); mirrored in
 // oracle/crbm_oracle.py.
 enum : uint32_t {
-  KIND_CHAIN_H = 1, KIND_CHAIN_V = 2, KIND_EVAL_H = 3, KIND_API_H = 4, KIND_API_V = 5
+  KIND_CHAIN_H = 1, KIND_CHAIN_V = 2, KIND_EVAL_H = 3, KIND_API_H = 4, KIND_API_V = 5,
+  KIND_AIS_H = 6, KIND_AIS_V = 7      // annealed importance sampling (crbm_ais), keyed by the seed of the call
 };
 
 // n / d via one mul_hi (d >= 1).  With inv = floor(2^32 / d) + 1 the estimate
@@ -186,6 +187,24 @@ inline GibbsLayout gibbs_layout(const ModelShape& ms, int Lf, int S, bool sparse
   g.lds_bytes = (int)(words * 4);
   return g;
 }
+
+// ---- annealed importance sampling (crbm_kernels.h, ais_body) ------------------------------
+// One wave owns a run for all steps of a launch.  Its LDS slice: the zero-padded hidden mask row of the forward
+// strand (Lrow positions of NW words, hidden position s at s + M-1, as in the chain kernel), that of the
+// reverse-complement strand (ds), the packed letter row (LWs words); rounded to 16 bytes.  In front of the
+// slices sit the gather table and the set-bit top-down tables (the image of the sparse chain kernel).
+struct AisLayout {
+  int nvb, Lrow, LWs, run_words;
+};
+inline AisLayout ais_layout(const ModelShape& ms, int L) {
+  AisLayout a;
+  a.nvb = cdiv(L, 4);
+  a.Lrow = 4 * cdiv(4 * a.nvb + ms.M - 1 + 3, 4);
+  a.LWs = letter_words(4 * a.nvb);
+  a.run_words = ((1 + ms.DS) * a.Lrow * ms.NW + a.LWs + 3) & ~3;
+  return a;
+}
+inline long ais_lds_bytes(const ModelShape& ms, const AisLayout& a, int waves) { return 4L * (ms.SP_TABLES + (long)waves * a.run_words); }
 
 // ---- MFMA statistics ----------------------------------------------------------------
 // Hidden positions are handled in groups of 32 (one MFMA step).  A chain of Lh hidden

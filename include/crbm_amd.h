@@ -242,6 +242,32 @@ int crbm_mutagenesis(crbm_handle* h, const float* v, int32_t n, int32_t L, float
 int crbm_mutagenesis_codes(crbm_handle* h, const uint8_t* codes, int32_t n, int32_t L, float* dfe, float* pll);
 int crbm_mutagenesis_resident(crbm_handle* h, int32_t start, int32_t end, float* dfe, float* pll);
 
+/* ---- annealed importance sampling: log Z and the normalised log-likelihood -------
+ * (Neal 2001; Salakhutdinov & Murray 2008.)  Models on the specialised kernels, DNA alphabet, pooling == 1.  With
+ * x, x' the bottom-up activations of the two strands (bias included, convRBM.py:238-243), S = 2 strands if
+ * doublestranded else 1 and Lh = L - motif_length + 1:
+ *   log p*_beta(v) = sum_{strands,k,s} softplus(beta x[k,s](v)) + sum_p (beta c[v_p] + (1 - beta) cA[v_p])
+ * log p*_1(v) = -L * crbm_free_energy(v); cA = base_c (4) is the visible bias of the base-rate model (NULL: the
+ * model's own c), whose partition function is log Z_A = L logsumexp(cA) + S K Lh ln 2.  The ladder betas[0..nbetas-1]
+ * is non-decreasing inside [0,1].  Run r (global index run_offset + r) draws v_0 ~ softmax(cA) and does, for step t,
+ *   logw += log p*_{betas[t+1]}(v_t) - log p*_{betas[t]}(v_t)
+ *   h, h' ~ Bernoulli(sigmoid(betas[t+1] x(v_t))),  v_{t+1} ~ softmax(betas[t+1] (c + W^T h + rc(W)^T h') + (1 - betas[t+1]) cA)
+ * with the counter layout and the 24-bit uniforms of the persistent chain under two kinds of their own (6: hidden,
+ * 7: visible), keyed by `seed`: sequence word run_offset + r, step word 0 for v_0 and t + 1 for step t.  With
+ * betas[0] = 0 and betas[nbetas-1] = 1, log Z ~= log Z_A + log mean_r exp(logw[r]) (the caller reduces, in double).
+ *
+ * crbm_ais does steps [t0,t1) of the ladder for `runs` runs.  t0 == 0: the runs start from the base-rate model and
+ * logw from 0; t0 > 0: `state` (runs,L) letter codes and `logw` are read and continued.  On return logw (runs) holds
+ * the accumulated log weights and state, if not NULL, v_{t1}.  The library cuts [t0,t1) into launches of at most
+ * CRBM_AIS_STEPS steps (environment, default 64); logw[r] and state[r] have the same bits for every such cut, every
+ * split of the runs over calls (run_offset) and every split of the ladder over calls.  The call reads the parameters
+ * and changes nothing else of the handle: chains, last visible sample, sampler counters, velocities and resident data
+ * sets are as before.  CRBM_ERR_INVALID: L < motif_length, runs <= 0, nbetas < 2, t0 / t1 outside
+ * 0 <= t0 < t1 <= nbetas-1, a ladder that decreases, leaves [0,1] or is not finite, t0 > 0 without state, a run that
+ * does not fit the LDS, pooling > 1, a model on the generic kernels, an alphabet other than DNA's. */
+int crbm_ais(crbm_handle* h, int32_t L, int32_t runs, uint32_t run_offset, const float* betas, int32_t nbetas,
+             int32_t t0, int32_t t1, const float* base_c, uint64_t seed, uint8_t* state, float* logw);
+
 /* ---- data-parallel (new: the reference is single-device) -----------------
  * One process per GPU.  Rank 0 calls crbm_comm_unique_id and distributes the
  * 128 bytes by any host channel; every rank then calls crbm_comm_init.  After
