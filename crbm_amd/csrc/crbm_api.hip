@@ -4,6 +4,7 @@
 #define CRBM_DEFINE_MISC_KERNELS
 #include "crbm_kernels.h"
 #include "crbm_jit.h"
+#include "crbm_sweep.h"
 #include "../../include/crbm_amd.h"
 
 #include <dlfcn.h>
@@ -166,14 +167,15 @@ struct crbm_handle {
   DevBuf<uint32_t> dataset[CRBM_DATASET_SLOTS];   // resident data sets (slot 0: training, slot 1: test by convention)
   DevBuf<float> partials, partials2;
   DevBuf<unsigned long long> eval_ones;            // sampled ones per mini-batch (crbm_eval_epoch_resident)
-  // motif sites (crbm_motif_sites*), one of each per set of a two-stream sweep: records, the slab's record counter,
-  // the best-site keys of the slab's (seq, motif)
-  DevBuf<SiteRec> site_recs[2];
-  DevBuf<unsigned long long> site_count[2], site_keys[2];
-  // in-silico mutagenesis (crbm_mutagenesis*), one of each per set of a two-stream sweep: dF and pll of a slab, and the
-  // expanded rows (base rows and their single-substitution copies) of the general path
-  DevBuf<float> mut_df[2], mut_pll[2];
-  DevBuf<uint32_t> mut_rows[2];
+  // What the features keep per set of a two-stream sweep (reached through sweep_set, never indexed beside it).  Motif
+  // sites: records, the slab's record counter, the best-site keys of the slab's (seq, motif).  Mutagenesis: dF and pll of a
+  // slab, and the expanded rows (base rows and their single-substitution copies) of the general path.
+  struct SetBufs {
+    DevBuf<SiteRec> site_recs;
+    DevBuf<unsigned long long> site_count, site_keys;
+    DevBuf<float> mut_df, mut_pll;
+    DevBuf<uint32_t> mut_rows;
+  } set_bufs[2];
   int mut_route = 0;                               // route of the last crbm_mutagenesis* call: 1 fused kernel, 2 general path
   // annealed importance sampling (crbm_ais): the ladder, cA, the runs' log weights and letter codes between launches
   DevBuf<float> ais_betas, ais_base, ais_logw;
@@ -480,36 +482,6 @@ int check_flags(crbm_handle* h) {
     return fail(h, CRBM_ERR_NOT_BINARY, "hidden state is not exactly 0/1");
   }
   return CRBM_OK;
-}
-
-// host one-hot (n,1,A,L) -> packed letters on the device
-int encode_host(crbm_handle* h, const float* v, int n, int L, uint32_t* d_letters) {
-  const size_t count = (size_t)n * h->A * L;
-  HIPCHK(h->stage.ensure(count));
-  HIPCHK(hipMemcpyAsync(h->stage.p, v, count * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  EncodeArgs a;
-  a.v = h->stage.p; a.letters = d_letters; a.flags = h->d_flags;
-  a.n = n; a.L = L; a.LW = lw(h, L); a.A = h->A;
-  const int grid = grid_for((long)n * a.LW, 256, h->num_cu * 8);
-  if (h->A == 4) hipLaunchKernelGGL(encode_onehot_kernel, dim3(grid), dim3(256), 0, h->stream, a);
-  else hipLaunchKernelGGL(encode_onehot_any_kernel, dim3(grid), dim3(256), 0, h->stream, a);
-  HIPCHK(hipGetLastError());
-  return check_flags(h);
-}
-
-// host bytes (n,L) -> packed letters on the device
-int encode_codes_host(crbm_handle* h, const uint8_t* codes, int n, int L, uint32_t* d_letters) {
-  const size_t bytes = (size_t)n * L;
-  HIPCHK(h->stage.ensure((bytes + 3) / 4));
-  HIPCHK(hipMemcpyAsync(h->stage.p, codes, bytes, hipMemcpyHostToDevice, h->stream));
-  EncodeCodesArgs a;
-  a.codes = reinterpret_cast<const unsigned char*>(h->stage.p);
-  a.letters = d_letters; a.flags = h->d_flags;
-  a.n = n; a.L = L; a.LW = lw(h, L); a.A = h->A;
-  if (h->A == 4) hipLaunchKernelGGL(encode_codes_kernel, dim3(grid_for((long)n * a.LW, 256, h->num_cu * 8)), dim3(256), 0, h->stream, a);
-  else hipLaunchKernelGGL(encode_codes_any_kernel, dim3(grid_for((long)n * a.LW, 256, h->num_cu * 8)), dim3(256), 0, h->stream, a);
-  HIPCHK(hipGetLastError());
-  return check_flags(h);
 }
 
 int launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int mode, float* act, float* prob,
@@ -1348,6 +1320,158 @@ int copy_out(crbm_handle* h, float* host, const float* dev, size_t count) {
   return CRBM_OK;
 }
 
+// where the letters of a call come from
+struct RowSource {
+  const float* onehot = nullptr;      // host (n,1,A,L) fp32
+  const uint8_t* codes = nullptr;     // host (n,L) bytes 0..A-1
+  const uint32_t* resident = nullptr; // device packed rows
+  int n = 0, L = 0, A = 4;
+  size_t in_bytes_per_row() const { return onehot ? (size_t)4 * A * L : (codes ? (size_t)L : 0); }
+};
+static RowSource host_onehot_(const float* v, int n, int L, int A) { RowSource s; s.onehot = v; s.n = n; s.L = L; s.A = A; return s; }
+static RowSource host_codes_(const uint8_t* c, int n, int L, int A) { RowSource s; s.codes = c; s.n = n; s.L = L; s.A = A; return s; }
+#define host_onehot(v, n, L) host_onehot_(v, n, L, h->A)
+#define host_codes(c, n, L) host_codes_(c, n, L, h->A)
+
+// ---- the two buffer sets of the evaluation sweeps -------------------------------------------------
+// An evaluation sweep walks its rows slab by slab through run_slabs (crbm_sweep.h; sweep_run below binds it to a
+// handle).  Slab i is staged, encoded and processed on the stream of set (i & 1) and in that set's buffers; its outputs
+// are collected only after slab i+1 has been enqueued, so the host->device copy of one slab overlaps the kernels of the
+// other.  Resident sources alternate too: slab i's outputs are still to be copied out when slab i+1 runs.  Three
+// invariants make this correct; the first is run_slabs' order of calls, the other two are the features' to keep:
+//   1. a set is reused only after its previous slab has been collected;
+//   2. nothing is (re)allocated while the other stream runs: whatever both sets write is sized for a whole slab before
+//      the sweep starts (an ensure() inside the loop then finds its buffer large enough);
+//   3. a slab's outputs are copied from the set that produced them, on that set's stream.
+// Everything a slab writes belongs to its set and is reached through sweep_set: staging and letters, the outputs oa / ob,
+// the per-motif scratch of the slabbed free energies (in the slab model's shadow handle), the features' own buffers.
+// Set 0 is the handle's main stream and buffers, which the calls outside the sweeps use as well.  What the two streams
+// share is read-only during a sweep (parameters, d_tables and d_slab_tables: sweep_begin builds them first) or combined
+// in any order (d_flags: atomicOr; the hit summary's position sums: 64-bit integer atomics).
+struct SweepSet {
+  hipStream_t st;
+  DevBuf<float>* stage;
+  DevBuf<uint32_t>* letters;
+  DevBuf<float>* oa;
+  DevBuf<float>* ob;
+  DevBuf<float>* fe_scratch;
+  crbm_handle::SetBufs* own;
+};
+SweepSet sweep_set(crbm_handle* h, int i) {
+  crbm_handle* s = h->slab;
+  if (i & 1) return SweepSet{h->stream2, &h->stage2, &h->letters2, &h->out_a2, &h->out_b2, s ? &s->out_b2 : nullptr, &h->set_bufs[1]};
+  return SweepSet{h->stream, &h->stage, &h->letters, &h->out_a, &h->out_b, s ? &s->out_b : nullptr, &h->set_bufs[0]};
+}
+
+// enqueue on the set's stream: rows [start, start+cnt) of a host source, through the set's staging buffer, as packed
+// letters at `dst` (no flag check)
+int encode_rows(crbm_handle* h, const RowSource& src, int start, int cnt, const SweepSet& set, uint32_t* dst) {
+  const int L = src.L, LW = lw(h, L);
+  const dim3 grid(grid_for((long)cnt * LW, 256, h->num_cu * 8));
+  if (src.onehot) {
+    const size_t count = (size_t)cnt * h->A * L;
+    HIPCHK(set.stage->ensure(count));
+    HIPCHK(hipMemcpyAsync(set.stage->p, src.onehot + (size_t)start * h->A * L, count * sizeof(float), hipMemcpyHostToDevice, set.st));
+    EncodeArgs a;
+    a.v = set.stage->p; a.letters = dst; a.flags = h->d_flags;
+    a.n = cnt; a.L = L; a.LW = LW; a.A = h->A;
+    if (h->A == 4) hipLaunchKernelGGL(encode_onehot_kernel, grid, dim3(256), 0, set.st, a);
+    else hipLaunchKernelGGL(encode_onehot_any_kernel, grid, dim3(256), 0, set.st, a);
+  } else {
+    const size_t bytes = (size_t)cnt * L;
+    HIPCHK(set.stage->ensure((bytes + 3) / 4));
+    HIPCHK(hipMemcpyAsync(set.stage->p, src.codes + (size_t)start * L, bytes, hipMemcpyHostToDevice, set.st));
+    EncodeCodesArgs a;
+    a.codes = reinterpret_cast<const unsigned char*>(set.stage->p);
+    a.letters = dst; a.flags = h->d_flags;
+    a.n = cnt; a.L = L; a.LW = LW; a.A = h->A;
+    if (h->A == 4) hipLaunchKernelGGL(encode_codes_kernel, grid, dim3(256), 0, set.st, a);
+    else hipLaunchKernelGGL(encode_codes_any_kernel, grid, dim3(256), 0, set.st, a);
+  }
+  HIPCHK(hipGetLastError());
+  return CRBM_OK;
+}
+
+// ... on the main stream, the validity flags checked at once; without a destination: into h->letters
+int encode_now(crbm_handle* h, const RowSource& src, int start, int cnt, uint32_t* dst = nullptr) {
+  if (!dst) {
+    HIPCHK(h->letters.ensure((size_t)cnt * lw(h, src.L)));
+    dst = h->letters.p;
+  }
+  const int rc = encode_rows(h, src, start, cnt, sweep_set(h, 0), dst);
+  return rc ? rc : check_flags(h);
+}
+
+// rows of a slab whose staged input plus outputs take `bytes_per_row`: the slab budget, CRBM_SLAB_BYTES or 256 MB
+int slab_rows(int n, size_t bytes_per_row) {
+  const size_t budget = (size_t)env_int("CRBM_SLAB_BYTES", 256 << 20);
+  size_t rows = budget / std::max<size_t>(bytes_per_row, 1);
+  if (rows < 1) rows = 1;
+  return (int)std::min<size_t>(rows, (size_t)n);
+}
+// rows per slab of a two-stream sweep: host input uses small slabs so that there is something to overlap
+int sweep_slab(const RowSource& src, size_t out_bytes_per_row) {
+  const size_t per_row = src.in_bytes_per_row() + out_bytes_per_row;
+  int slab = slab_rows(src.n, per_row);
+  if (!src.resident && !getenv("CRBM_SLAB_BYTES")) slab = std::min<size_t>(slab, std::max<size_t>(1, (32u << 20) / std::max<size_t>(per_row, 1)));
+  return slab;
+}
+// tables built and visible to both streams before a sweep starts (the slab tables of a generic DNA model too: a slab on
+// the second stream must not find them being rebuilt on the main one)
+int sweep_begin(crbm_handle* h) {
+  int rc = ensure_tables(h);
+  if (rc) return rc;
+  if (h->slab) {
+    rc = slab_ensure_tables(h, h->stream);
+    if (rc) return rc;
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return CRBM_OK;
+}
+// both streams idle, then the one-hot / code validity flags of every slab at once
+int sweep_finish(crbm_handle* h, const RowSource& src) {
+  HIPCHK(hipStreamSynchronize(h->stream2));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return src.resident ? CRBM_OK : check_flags(h);
+}
+// a sweep that failed half-way: whatever it has enqueued runs out before the next call resizes a buffer under it, and no
+// validity flag stays raised for the next call to trip over (the error already stands in h->err)
+void sweep_drain(crbm_handle* h) {
+  (void)hipStreamSynchronize(h->stream2);
+  (void)hipStreamSynchronize(h->stream);
+  (void)hipMemsetAsync(h->d_flags, 0, sizeof(uint32_t), h->stream);
+  (void)hipStreamSynchronize(h->stream);
+}
+
+// run_slabs over a source, in slabs of `slab` rows.  launch(set, rows, start, cnt) enqueues the kernels of rows
+// [start, start+cnt) on `set`; `rows` are their packed letters, a resident source's own or a host source's staged and
+// encoded into the set's letters just before.  collect(set, rows, start, cnt) copies that slab's outputs out on the
+// set's stream and waits for them.  Depth 2 (after sweep_begin): the two streams, the validity flags of all slabs checked
+// at the end.  Depth 1: the main stream alone, the flags of each slab checked before its kernels go out.  The staging and
+// letter buffers of every set in use are sized here, before anything runs; what the launches write is the caller's to size.
+template <class Launch, class Collect>
+int sweep_run(crbm_handle* h, const RowSource& src, int slab, int depth, Launch launch, Collect collect) {
+  const int LW = lw(h, src.L);
+  for (int s = 0; s < (depth == 2 && slab < src.n ? 2 : 1) && !src.resident; ++s) {
+    const SweepSet set = sweep_set(h, s);
+    HIPCHK(set.letters->ensure((size_t)slab * LW));
+    HIPCHK(set.stage->ensure(src.onehot ? (size_t)slab * h->A * src.L : ((size_t)slab * src.L + 3) / 4));
+  }
+  const uint32_t* rows[2] = {nullptr, nullptr};
+  const int rc = run_slabs(src.n, slab, depth,
+    [&](int, int s, int start, int cnt) -> int {
+      const SweepSet set = sweep_set(h, s);
+      rows[s] = src.resident ? src.resident + (size_t)start * LW : set.letters->p;
+      int r = src.resident ? CRBM_OK : encode_rows(h, src, start, cnt, set, set.letters->p);
+      if (!r && depth == 1 && !src.resident) r = check_flags(h);
+      return r ? r : launch(set, rows[s], start, cnt);
+    },
+    [&](int, int s, int start, int cnt) -> int { return collect(sweep_set(h, s), rows[s], start, cnt); },
+    [&] { sweep_drain(h); });
+  if (rc || depth == 1) return rc;
+  return sweep_finish(h, src);
+}
+
 }  // namespace
 
 // =============================================================================
@@ -1779,8 +1903,10 @@ int crbm_destroy(crbm_handle* h) {
   h->stage.release(); h->stage2.release(); h->out_a.release(); h->out_b.release(); h->out_c.release();
   h->letters.release(); h->letters2.release(); h->masks_tmp.release(); h->out_a2.release(); h->out_b2.release();
   for (auto& d : h->dataset) d.release(); h->partials.release(); h->partials2.release();
-  for (int i = 0; i < 2; ++i) { h->site_recs[i].release(); h->site_count[i].release(); h->site_keys[i].release(); }
-  for (int i = 0; i < 2; ++i) { h->mut_df[i].release(); h->mut_pll[i].release(); h->mut_rows[i].release(); }
+  for (auto& b : h->set_bufs) {
+    b.site_recs.release(); b.site_count.release(); b.site_keys.release();
+    b.mut_df.release(); b.mut_pll.release(); b.mut_rows.release();
+  }
   h->ais_betas.release(); h->ais_base.release(); h->ais_logw.release(); h->ais_state.release();
   if (h->jk.module) (void)hipModuleUnload(h->jk.module);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1929,8 +2055,7 @@ int crbm_train_step(crbm_handle* h, const float* D, int32_t n, int32_t L) {
   ARGCHK(D, "null argument");
   int rc = check_data_shape(h, n, L);
   if (rc) return rc;
-  HIPCHK(h->letters.ensure((size_t)n * lw(h, L)));
-  rc = encode_host(h, D, n, L, h->letters.p);
+  rc = encode_now(h, host_onehot(D, n, L), 0, n);
   if (rc) return rc;
   rc = train_core(h, h->letters.p, n, L);
   if (rc) return rc;
@@ -1956,9 +2081,10 @@ int crbm_dataset_upload(crbm_handle* h, const float* data, int32_t n, int32_t L)
   HIPCHK(ds.ensure((size_t)n * LW));
   // stream the fp32 array through the staging buffer in slabs of <= 64 MiB
   const int slab = std::max(1, (int)std::min<long>(n, (64L << 20) / ((long)h->A * L * 4)));
+  const RowSource src = host_onehot(data, n, L);
   for (int start = 0; start < n; start += slab) {
     const int cnt = std::min(slab, n - start);
-    rc = encode_host(h, data + (size_t)start * h->A * L, cnt, L, ds.p + (size_t)start * LW);
+    rc = encode_now(h, src, start, cnt, ds.p + (size_t)start * LW);
     if (rc) return rc;
   }
   h->dataset_n[h->slot] = n; h->dataset_L[h->slot] = L;
@@ -1975,9 +2101,10 @@ int crbm_dataset_upload_codes(crbm_handle* h, const uint8_t* codes, int32_t n, i
   h->dataset_n[h->slot] = 0;
   HIPCHK(ds.ensure((size_t)n * LW));
   const int slab = std::max(1, (int)std::min<long>(n, (256L << 20) / (long)L));
+  const RowSource src = host_codes(codes, n, L);
   for (int start = 0; start < n; start += slab) {
     const int cnt = std::min(slab, n - start);
-    rc = encode_codes_host(h, codes + (size_t)start * L, cnt, L, ds.p + (size_t)start * LW);
+    rc = encode_now(h, src, start, cnt, ds.p + (size_t)start * LW);
     if (rc) return rc;
   }
   h->dataset_n[h->slot] = n; h->dataset_L[h->slot] = L;
@@ -2204,8 +2331,7 @@ int crbm_h_given_v(crbm_handle* h, const float* v, int32_t n, int32_t L, int32_t
   if (rc) return rc;
   const int Lh = L - h->M + 1;
   const size_t count = (size_t)n * h->K * Lh;
-  HIPCHK(h->letters.ensure((size_t)n * lw(h, L)));
-  rc = encode_host(h, v, n, L, h->letters.p);
+  rc = encode_now(h, host_onehot(v, n, L), 0, n);
   if (rc) return rc;
   if (act) HIPCHK(h->out_a.ensure(count));
   if (prob) HIPCHK(h->out_b.ensure(count));
@@ -2269,37 +2395,9 @@ int crbm_v_given_h(crbm_handle* h, const float* hid, const float* hid_prime, int
 // (the reference's layout), one byte per base host input (`_codes`), and rows of
 // a data set already resident in HBM (`_resident`).  Host input is streamed in
 // slabs so that the staged input plus the outputs of one slab stay around
-// 256 MB (data sets far larger than the scratch: SURVEY 8(f)-1).
-static int slab_rows(int n, size_t bytes_per_row) {
-  const size_t budget = (size_t)env_int("CRBM_SLAB_BYTES", 256 << 20);
-  size_t rows = budget / std::max<size_t>(bytes_per_row, 1);
-  if (rows < 1) rows = 1;
-  return (int)std::min<size_t>(rows, (size_t)n);
-}
-
+// 256 MB (data sets far larger than the scratch: SURVEY 8(f)-1): slab_rows gives
+// the slab, sweep_run walks the slabs.
 namespace {
-
-// where the letters of an evaluation call come from
-struct RowSource {
-  const float* onehot = nullptr;      // host (n,1,A,L) fp32
-  const uint8_t* codes = nullptr;     // host (n,L) bytes 0..A-1
-  const uint32_t* resident = nullptr; // device packed rows
-  int n = 0, L = 0, A = 4;
-  size_t in_bytes_per_row() const { return onehot ? (size_t)4 * A * L : (codes ? (size_t)L : 0); }
-};
-
-// packed letters of rows [start, start+cnt) of a source; host sources go through h->letters
-int source_rows(crbm_handle* h, const RowSource& src, int start, int cnt, const uint32_t** out) {
-  const int LW = lw(h, src.L);
-  if (src.resident) {
-    *out = src.resident + (size_t)start * LW;
-    return CRBM_OK;
-  }
-  HIPCHK(h->letters.ensure((size_t)cnt * LW));
-  *out = h->letters.p;
-  if (src.onehot) return encode_host(h, src.onehot + (size_t)start * h->A * src.L, cnt, src.L, h->letters.p);
-  return encode_codes_host(h, src.codes + (size_t)start * src.L, cnt, src.L, h->letters.p);
-}
 
 int resident_source(crbm_handle* h, int start, int end, RowSource* src) {
   const int slot = h->slot;
@@ -2311,87 +2409,6 @@ int resident_source(crbm_handle* h, int start, int end, RowSource* src) {
   return CRBM_OK;
 }
 
-// ---- double-buffered sweeps over host input ---------------------
-// Slab i is staged, encoded and processed on stream (i & 1) with buffer set (i & 1);
-// its outputs are collected only after slab i+1 has been enqueued, so the host->device
-// copy of one slab overlaps the kernels of the other.  Resident sources alternate too: slab i's outputs are still to be
-// copied out when slab i+1 runs, so the two must not share an output buffer.
-// Everything a slab writes belongs to its set: the staging and letter buffers, the outputs and the per-motif scratch of
-// the slabbed free energies (fe_scratch, in the slab model's shadow handle).  What the two streams share is read-only
-// during a sweep (parameters, d_tables and d_slab_tables: sweep_begin builds them first) or combined in any order
-// (d_flags: atomicOr; the hit summary's position sums: 64-bit integer atomics).
-struct SweepSet {
-  hipStream_t st;
-  DevBuf<float>* stage;
-  DevBuf<uint32_t>* letters;
-  DevBuf<float>* oa;
-  DevBuf<float>* ob;
-  DevBuf<float>* fe_scratch;
-};
-SweepSet sweep_set(crbm_handle* h, int i) {
-  crbm_handle* s = h->slab;
-  if (i & 1) return SweepSet{h->stream2, &h->stage2, &h->letters2, &h->out_a2, &h->out_b2, s ? &s->out_b2 : nullptr};
-  return SweepSet{h->stream, &h->stage, &h->letters, &h->out_a, &h->out_b, s ? &s->out_b : nullptr};
-}
-// rows per slab: host input uses small slabs so that there is something to overlap
-int sweep_slab(const RowSource& src, size_t out_bytes_per_row) {
-  const size_t per_row = src.in_bytes_per_row() + out_bytes_per_row;
-  int slab = slab_rows(src.n, per_row);
-  if (!src.resident && !getenv("CRBM_SLAB_BYTES")) slab = std::min<size_t>(slab, std::max<size_t>(1, (32u << 20) / std::max<size_t>(per_row, 1)));
-  return slab;
-}
-// enqueue staging + encoding of rows [start, start+cnt) on the set's stream (no flag check: sweep_finish)
-int sweep_rows(crbm_handle* h, const RowSource& src, int start, int cnt, const SweepSet& set, const uint32_t** out) {
-  const int L = src.L, LW = lw(h, L);
-  if (src.resident) {
-    *out = src.resident + (size_t)start * LW;
-    return CRBM_OK;
-  }
-  HIPCHK(set.letters->ensure((size_t)cnt * LW));
-  *out = set.letters->p;
-  const int grid = grid_for((long)cnt * LW, 256, h->num_cu * 8);
-  if (src.onehot) {
-    const size_t count = (size_t)cnt * h->A * L;
-    HIPCHK(set.stage->ensure(count));
-    HIPCHK(hipMemcpyAsync(set.stage->p, src.onehot + (size_t)start * h->A * L, count * sizeof(float), hipMemcpyHostToDevice, set.st));
-    EncodeArgs a;
-    a.v = set.stage->p; a.letters = set.letters->p; a.flags = h->d_flags;
-    a.n = cnt; a.L = L; a.LW = LW; a.A = h->A;
-    if (h->A == 4) hipLaunchKernelGGL(encode_onehot_kernel, dim3(grid), dim3(256), 0, set.st, a);
-    else hipLaunchKernelGGL(encode_onehot_any_kernel, dim3(grid), dim3(256), 0, set.st, a);
-  } else {
-    const size_t bytes = (size_t)cnt * L;
-    HIPCHK(set.stage->ensure((bytes + 3) / 4));
-    HIPCHK(hipMemcpyAsync(set.stage->p, src.codes + (size_t)start * L, bytes, hipMemcpyHostToDevice, set.st));
-    EncodeCodesArgs a;
-    a.codes = reinterpret_cast<const unsigned char*>(set.stage->p);
-    a.letters = set.letters->p; a.flags = h->d_flags;
-    a.n = cnt; a.L = L; a.LW = LW; a.A = h->A;
-    if (h->A == 4) hipLaunchKernelGGL(encode_codes_kernel, dim3(grid), dim3(256), 0, set.st, a);
-    else hipLaunchKernelGGL(encode_codes_any_kernel, dim3(grid), dim3(256), 0, set.st, a);
-  }
-  HIPCHK(hipGetLastError());
-  return CRBM_OK;
-}
-// tables built and visible to both streams before a sweep starts (the slab tables of a generic DNA model too: a slab on
-// the second stream must not find them being rebuilt on the main one)
-int sweep_begin(crbm_handle* h) {
-  int rc = ensure_tables(h);
-  if (rc) return rc;
-  if (h->slab) {
-    rc = slab_ensure_tables(h, h->stream);
-    if (rc) return rc;
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return CRBM_OK;
-}
-// both streams idle, then the one-hot / code validity flags of every slab at once
-int sweep_finish(crbm_handle* h, const RowSource& src) {
-  HIPCHK(hipStreamSynchronize(h->stream2));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return src.resident ? CRBM_OK : check_flags(h);
-}
-
 int hit_probs_any(crbm_handle* h, const RowSource& src, float* out) {
   int rc = check_data_shape(h, src.n, src.L);
   if (rc) return rc;
@@ -2399,24 +2416,21 @@ int hit_probs_any(crbm_handle* h, const RowSource& src, float* out) {
   const size_t per_seq_out = (size_t)h->K * Lh;
   const int slab = slab_rows(src.n, src.in_bytes_per_row() + per_seq_out * sizeof(float));
   HIPCHK(h->out_b.ensure((size_t)slab * per_seq_out));
-  for (int start = 0; start < src.n; start += slab) {
-    const int cnt = std::min(slab, src.n - start);
-    const uint32_t* rows = nullptr;
-    rc = source_rows(h, src, start, cnt, &rows);
-    if (rc) return rc;
-    // convRBM.py:507-514: doublestranded -> sigma(x); single-stranded -> sigma(x + x')
-    rc = launch_hgv(h, rows, cnt, L, h->ds ? 0 : 2, nullptr, h->out_b.p, nullptr, nullptr, KIND_API_H, 0, 0);
-    if (rc) return rc;
-    rc = copy_out(h, out + (size_t)start * per_seq_out, h->out_b.p, (size_t)cnt * per_seq_out);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return CRBM_OK;
+  return sweep_run(h, src, slab, 1,
+    [&](const SweepSet& set, const uint32_t* rows, int, int cnt) -> int {
+      // convRBM.py:507-514: doublestranded -> sigma(x); single-stranded -> sigma(x + x')
+      return launch_hgv(h, rows, cnt, L, h->ds ? 0 : 2, nullptr, set.ob->p, nullptr, nullptr, KIND_API_H, 0, 0);
+    },
+    [&](const SweepSet& set, const uint32_t*, int start, int cnt) -> int {
+      HIPCHK(hipMemcpyAsync(out + (size_t)start * per_seq_out, set.ob->p, (size_t)cnt * per_seq_out * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      HIPCHK(hipStreamSynchronize(set.st));
+      return CRBM_OK;
+    });
 }
 
 // free energies of n packed rows into the set's outputs (per sequence / per motif), no copy
 int launch_free_energy(crbm_handle* h, const uint32_t* rows, int n, int L, const SweepSet& set) {
-  int rc = ensure_tables(h);   // no-op inside a sweep (sweep_begin has done it)
+  int rc = ensure_tables(h);   // no-op inside a two-stream sweep (sweep_begin has done it)
   if (rc) return rc;
   HIPCHK(set.oa->ensure((size_t)n));
   HIPCHK(set.ob->ensure((size_t)n * h->K));
@@ -2436,38 +2450,21 @@ int free_energy_any(crbm_handle* h, const RowSource& src, float* fe, float* fem)
   if (rc) return rc;
   rc = sweep_begin(h);
   if (rc) return rc;
-  const int slab = sweep_slab(src, ((size_t)h->K + 1) * sizeof(float));
-  if (slab_fe_on(h)) {
-    // the slabbed free energies' scratch of both sets at its largest before either stream starts: no ensure() inside the
-    // loop reallocates a buffer while kernels of the other stream run
-    const size_t scratch = (size_t)slab * h->slab->K * h->slab_n;
-    HIPCHK(h->slab->out_b.ensure(scratch));
-    if (slab < src.n) HIPCHK(h->slab->out_b2.ensure(scratch));
-  }
-  int prev_start = -1, prev_cnt = 0;
-  SweepSet prev = sweep_set(h, 0);
-  auto collect = [&]() -> int {     // outputs of the previous slab -> host
-    if (prev_start < 0) return CRBM_OK;
-    if (fe) HIPCHK(hipMemcpyAsync(fe + prev_start, prev.oa->p, (size_t)prev_cnt * sizeof(float), hipMemcpyDeviceToHost, prev.st));
-    if (fem) HIPCHK(hipMemcpyAsync(fem + (size_t)prev_start * h->K, prev.ob->p, (size_t)prev_cnt * h->K * sizeof(float), hipMemcpyDeviceToHost, prev.st));
-    HIPCHK(hipStreamSynchronize(prev.st));
-    return CRBM_OK;
-  };
-  for (int start = 0, i = 0; start < src.n; start += slab, ++i) {
-    const int cnt = std::min(slab, src.n - start);
+  const int K = h->K, slab = sweep_slab(src, ((size_t)K + 1) * sizeof(float));
+  for (int i = 0; i < (slab < src.n ? 2 : 1); ++i) {        // everything both streams write, at its size, before either starts
     const SweepSet set = sweep_set(h, i);
-    const uint32_t* rows = nullptr;
-    rc = sweep_rows(h, src, start, cnt, set, &rows);
-    if (rc) return rc;
-    rc = launch_free_energy(h, rows, cnt, src.L, set);
-    if (rc) return rc;
-    rc = collect();
-    if (rc) return rc;
-    prev = set; prev_start = start; prev_cnt = cnt;
+    HIPCHK(set.oa->ensure((size_t)slab));
+    HIPCHK(set.ob->ensure((size_t)slab * K));
+    if (slab_fe_on(h)) HIPCHK(set.fe_scratch->ensure((size_t)slab * h->slab->K * h->slab_n));
   }
-  rc = collect();
-  if (rc) return rc;
-  return sweep_finish(h, src);
+  return sweep_run(h, src, slab, 2,
+    [&](const SweepSet& set, const uint32_t* rows, int, int cnt) -> int { return launch_free_energy(h, rows, cnt, src.L, set); },
+    [&](const SweepSet& set, const uint32_t*, int start, int cnt) -> int {
+      if (fe) HIPCHK(hipMemcpyAsync(fe + start, set.oa->p, (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      if (fem) HIPCHK(hipMemcpyAsync(fem + (size_t)start * K, set.ob->p, (size_t)cnt * K * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      HIPCHK(hipStreamSynchronize(set.st));
+      return CRBM_OK;
+    });
 }
 
 int eval_data_any(crbm_handle* h, const RowSource& src, float* mfe, float* nmh) {
@@ -2478,21 +2475,19 @@ int eval_data_any(crbm_handle* h, const RowSource& src, float* mfe, float* nmh) 
   std::vector<float> fe((size_t)slab);
   double tot = 0.0;
   HIPCHK(hipMemsetAsync(h->d_ones, 0, sizeof(unsigned long long), h->stream));
-  for (int start = 0; start < n; start += slab) {
-    const int cnt = std::min(slab, n - start);
-    const uint32_t* rows = nullptr;
-    rc = source_rows(h, src, start, cnt, &rows);
-    if (rc) return rc;
-    rc = launch_free_energy(h, rows, cnt, L, sweep_set(h, 0));
-    if (rc) return rc;
-    rc = copy_out(h, fe.data(), h->out_a.p, (size_t)cnt);
-    if (rc) return rc;
-    // mean of a fresh forward-strand sample (convRBM.py:469-472); rows keep their index within the call
-    rc = launch_hgv(h, rows, cnt, L, 0, nullptr, nullptr, nullptr, h->d_ones, KIND_EVAL_H, h->eval_step, (uint32_t)start);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < cnt; ++i) tot += fe[i];
-  }
+  rc = sweep_run(h, src, slab, 1,
+    [&](const SweepSet& set, const uint32_t* rows, int start, int cnt) -> int {
+      const int r = launch_free_energy(h, rows, cnt, L, set);
+      // mean of a fresh forward-strand sample (convRBM.py:469-472); rows keep their index within the call
+      return r ? r : launch_hgv(h, rows, cnt, L, 0, nullptr, nullptr, nullptr, h->d_ones, KIND_EVAL_H, h->eval_step, (uint32_t)start);
+    },
+    [&](const SweepSet& set, const uint32_t*, int, int cnt) -> int {
+      HIPCHK(hipMemcpyAsync(fe.data(), set.oa->p, (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      HIPCHK(hipStreamSynchronize(set.st));
+      for (int i = 0; i < cnt; ++i) tot += fe[i];
+      return CRBM_OK;
+    });
+  if (rc) return rc;
   *mfe = (float)(tot / n);                       // convRBM.py:636-638
   h->eval_step += 1;
   unsigned long long ones = 0;
@@ -2524,55 +2519,45 @@ int hit_summary_any(crbm_handle* h, const RowSource& src, float* hmax, float* hm
   rc = sweep_begin(h);          // also orders the memset before both streams' kernels
   if (rc) return rc;
   const int slab = sweep_slab(src, (size_t)2 * K * sizeof(float));
-  int prev_start = -1, prev_cnt = 0;
-  SweepSet prev = sweep_set(h, 0);
+  for (int i = 0; i < (slab < n ? 2 : 1); ++i) {        // everything both streams write, at its size, before either starts
+    HIPCHK(sweep_set(h, i).oa->ensure((size_t)slab * K));
+    HIPCHK(sweep_set(h, i).ob->ensure((size_t)slab * K * (nchunks > 1 ? 3 : 1)));
+  }
   // layout of a set's `ob` when the positions come in several chunks: [cnt*K fixed-point sums][cnt*K means]
   auto mean_of = [&](const SweepSet& set, int cnt) { return nchunks > 1 ? set.ob->p + (size_t)2 * cnt * K : set.ob->p; };
-  auto collect = [&]() -> int {
-    if (prev_start < 0) return CRBM_OK;
-    if (hmax) HIPCHK(hipMemcpyAsync(hmax + (size_t)prev_start * K, prev.oa->p, (size_t)prev_cnt * K * sizeof(float), hipMemcpyDeviceToHost, prev.st));
-    if (hmean) HIPCHK(hipMemcpyAsync(hmean + (size_t)prev_start * K, mean_of(prev, prev_cnt), (size_t)prev_cnt * K * sizeof(float), hipMemcpyDeviceToHost, prev.st));
-    HIPCHK(hipStreamSynchronize(prev.st));
-    return CRBM_OK;
-  };
-  for (int start = 0, i = 0; start < n; start += slab, ++i) {
-    const int cnt = std::min(slab, n - start);
-    const SweepSet set = sweep_set(h, i);
-    const uint32_t* rows = nullptr;
-    rc = sweep_rows(h, src, start, cnt, set, &rows);
-    if (rc) return rc;
-    HIPCHK(set.oa->ensure((size_t)cnt * K));
-    HIPCHK(set.ob->ensure((size_t)cnt * K * (nchunks > 1 ? 3 : 1)));
-    if (nchunks > 1) {
-      HIPCHK(hipMemsetAsync(set.oa->p, 0, (size_t)cnt * K * 4, set.st));
-      HIPCHK(hipMemsetAsync(set.ob->p, 0, (size_t)cnt * K * 8, set.st));
-    }
-    HitArgs a;
-    a.tables = h->d_tables; a.letters = rows;
-    a.n = cnt; a.L = L; a.Lh = Lh; a.LW = lw(h, L);
-    a.hmax = hmax ? set.oa->p : nullptr;
-    a.hsum = (hmean && nchunks == 1) ? set.ob->p : nullptr;
-    a.hsum_fx = (hmean && nchunks > 1) ? reinterpret_cast<unsigned long long*>(set.ob->p) : nullptr;
-    a.inv_Lh = 1.0f / (float)Lh;
-    a.pos_fx = pos_fx;                          // both streams add (integers: any order)
-    const unsigned gx = (unsigned)std::max(1, std::min((cnt + 3) / 4, std::max(1, h->num_cu * 8 / nchunks)));
-    if (h->big) {
-      rc = big_launch_eval(h, rows, cnt, L, 1, nullptr, nullptr, a.hmax, a.hsum, pos_fx, nullptr, set.st);
-      if (rc) return rc;
-    } else
-    HIPCHK(jit_launch(h->jk.hit_summary, a, gx, (unsigned)nchunks, 256, lds, set.st));
-    if (a.hsum_fx) {
-      hipLaunchKernelGGL(hit_finalize_kernel, dim3(grid_for((long)cnt * K, 256, h->num_cu * 4)), dim3(256), 0, set.st, a.hsum_fx,
-                         mean_of(set, cnt), (size_t)cnt * K, a.inv_Lh / HIT_FX);
-      HIPCHK(hipGetLastError());
-    }
-    rc = collect();
-    if (rc) return rc;
-    prev = set; prev_start = start; prev_cnt = cnt;
-  }
-  rc = collect();
-  if (rc) return rc;
-  rc = sweep_finish(h, src);
+  rc = sweep_run(h, src, slab, 2,
+    [&](const SweepSet& set, const uint32_t* rows, int, int cnt) -> int {
+      if (nchunks > 1) {
+        HIPCHK(hipMemsetAsync(set.oa->p, 0, (size_t)cnt * K * 4, set.st));
+        HIPCHK(hipMemsetAsync(set.ob->p, 0, (size_t)cnt * K * 8, set.st));
+      }
+      HitArgs a;
+      a.tables = h->d_tables; a.letters = rows;
+      a.n = cnt; a.L = L; a.Lh = Lh; a.LW = lw(h, L);
+      a.hmax = hmax ? set.oa->p : nullptr;
+      a.hsum = (hmean && nchunks == 1) ? set.ob->p : nullptr;
+      a.hsum_fx = (hmean && nchunks > 1) ? reinterpret_cast<unsigned long long*>(set.ob->p) : nullptr;
+      a.inv_Lh = 1.0f / (float)Lh;
+      a.pos_fx = pos_fx;                          // both streams add (integers: any order)
+      const unsigned gx = (unsigned)std::max(1, std::min((cnt + 3) / 4, std::max(1, h->num_cu * 8 / nchunks)));
+      if (h->big) {
+        const int r = big_launch_eval(h, rows, cnt, L, 1, nullptr, nullptr, a.hmax, a.hsum, pos_fx, nullptr, set.st);
+        if (r) return r;
+      } else
+      HIPCHK(jit_launch(h->jk.hit_summary, a, gx, (unsigned)nchunks, 256, lds, set.st));
+      if (a.hsum_fx) {
+        hipLaunchKernelGGL(hit_finalize_kernel, dim3(grid_for((long)cnt * K, 256, h->num_cu * 4)), dim3(256), 0, set.st, a.hsum_fx,
+                           mean_of(set, cnt), (size_t)cnt * K, a.inv_Lh / HIT_FX);
+        HIPCHK(hipGetLastError());
+      }
+      return CRBM_OK;
+    },
+    [&](const SweepSet& set, const uint32_t*, int start, int cnt) -> int {
+      if (hmax) HIPCHK(hipMemcpyAsync(hmax + (size_t)start * K, set.oa->p, (size_t)cnt * K * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      if (hmean) HIPCHK(hipMemcpyAsync(hmean + (size_t)start * K, mean_of(set, cnt), (size_t)cnt * K * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      HIPCHK(hipStreamSynchronize(set.st));
+      return CRBM_OK;
+    });
   if (rc) return rc;
   if (posmean) {
     std::vector<unsigned long long> fx((size_t)K * Lh);
@@ -2605,12 +2590,12 @@ void sort_sites(const std::vector<SiteRec>& in, int nrows, std::vector<SiteRec>*
     if (first[i + 1] - first[i] > 1) std::sort(out->begin() + first[i], out->begin() + first[i + 1], before);
 }
 
-// Thresholded sites and best sites over a source, slab by slab on the two streams of a sweep.  Specialised models: the
-// fused crbm_motif_sites pass (motif_sites_body).  Generic models (h->big): the dense h|v of hit_probs_any into the set's
-// outputs (oa: the forward strand, or sigma(x + x') single-stranded; ob: the reverse-complemented filter), then
-// motif_sites_select_kernel.  Every set owns its records, counter and keys (sized before the loop); a slab whose count
-// exceeds its set's record buffer is run again into a larger one before anything is copied (its rows are still in the
-// set's buffers: the set is next used by the slab after the one enqueued before this collect).
+// Thresholded sites and best sites over a source, a two-stream sweep.  Specialised models: the fused crbm_motif_sites
+// pass (motif_sites_body).  Generic models (h->big): the dense h|v of hit_probs_any into the set's outputs (oa: the
+// forward strand, or sigma(x + x') single-stranded; ob: the reverse-complemented filter), then motif_sites_select_kernel.
+// Every set owns its records, counter and keys (sized before the sweep); a slab whose count exceeds its set's record
+// buffer is run again into a larger one before anything is copied (its rows are still in the set's buffers: the set is
+// next used by the slab after the one enqueued before this collect).
 int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64_t capacity, crbm_site* sites,
                     int64_t* count, int32_t* best_start, int32_t* best_strand, float* best_prob) {
   ARGCHK(threshold >= 0.f && threshold <= 1.f, "threshold must lie in [0, 1]");   // (NaN fails both)
@@ -2629,27 +2614,25 @@ int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64
   if (rc) return rc;
   const size_t dense_per_row = h->big ? (size_t)S * K * Lh * sizeof(float) : 0;
   const int slab = sweep_slab(src, (size_t)K * 8 + dense_per_row);
-  const int nsets = slab < n ? 2 : 1;
   const size_t rec0 = std::min((size_t)slab * K * S * Lh, std::max<size_t>((size_t)1 << 16, (size_t)4 * slab * K));
-  for (int i = 0; i < nsets; ++i) {        // everything both streams write, at its size, before either starts
+  for (int i = 0; i < (slab < n ? 2 : 1); ++i) {        // everything both streams write, at its size, before either starts
     const SweepSet set = sweep_set(h, i);
     if (want_recs) {
-      HIPCHK(h->site_recs[i].ensure(rec0));
-      HIPCHK(h->site_count[i].ensure(1));
+      HIPCHK(set.own->site_recs.ensure(rec0));
+      HIPCHK(set.own->site_count.ensure(1));
     }
-    if (want_best) HIPCHK(h->site_keys[i].ensure((size_t)slab * K));
+    if (want_best) HIPCHK(set.own->site_keys.ensure((size_t)slab * K));
     if (h->big) {
       HIPCHK(set.oa->ensure((size_t)slab * K * Lh));
       if (S == 2) HIPCHK(set.ob->ensure((size_t)slab * K * Lh));
     }
   }
-  auto launch = [&](int i, const uint32_t* rows, int cnt) -> int {
-    const SweepSet set = sweep_set(h, i & 1);
+  auto launch = [&](const SweepSet& set, const uint32_t* rows, int, int cnt) -> int {
     SitesOut o;
-    o.recs = want_recs ? h->site_recs[i & 1].p : nullptr;
-    o.capacity = want_recs ? h->site_recs[i & 1].cap : 0;
-    o.count = want_recs ? h->site_count[i & 1].p : nullptr;
-    o.best = want_best ? h->site_keys[i & 1].p : nullptr;
+    o.recs = want_recs ? set.own->site_recs.p : nullptr;
+    o.capacity = want_recs ? set.own->site_recs.cap : 0;
+    o.count = want_recs ? set.own->site_count.p : nullptr;
+    o.best = want_best ? set.own->site_keys.p : nullptr;
     o.threshold = threshold;
     if (want_recs) HIPCHK(hipMemsetAsync(o.count, 0, sizeof(unsigned long long), set.st));
     if (h->big) {
@@ -2675,42 +2658,37 @@ int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64
     return CRBM_OK;
   };
   int64_t total = 0;
-  int prev_i = -1, prev_start = 0, prev_cnt = 0;
-  const uint32_t* prev_rows = nullptr;
   std::vector<SiteRec> raw, sorted;
   std::vector<unsigned long long> keys;
-  auto collect = [&]() -> int {
-    if (prev_i < 0) return CRBM_OK;
-    const int si = prev_i & 1;
-    const SweepSet set = sweep_set(h, si);
+  auto collect = [&](const SweepSet& set, const uint32_t* rows, int start, int cnt) -> int {
     if (want_best) {
-      keys.resize((size_t)prev_cnt * K);
-      HIPCHK(hipMemcpyAsync(keys.data(), h->site_keys[si].p, keys.size() * 8, hipMemcpyDeviceToHost, set.st));
+      keys.resize((size_t)cnt * K);
+      HIPCHK(hipMemcpyAsync(keys.data(), set.own->site_keys.p, keys.size() * 8, hipMemcpyDeviceToHost, set.st));
     }
     unsigned long long c = 0;
-    if (want_recs) HIPCHK(hipMemcpyAsync(&c, h->site_count[si].p, sizeof(c), hipMemcpyDeviceToHost, set.st));
+    if (want_recs) HIPCHK(hipMemcpyAsync(&c, set.own->site_count.p, sizeof(c), hipMemcpyDeviceToHost, set.st));
     HIPCHK(hipStreamSynchronize(set.st));
     if (want_recs && total < capacity) {
-      if (c > h->site_recs[si].cap) {       // more records than the set's buffer took: again, into one that takes them
-        HIPCHK(h->site_recs[si].ensure((size_t)c));
-        rc = launch(prev_i, prev_rows, prev_cnt);
-        if (rc) return rc;
+      if (c > set.own->site_recs.cap) {       // more records than the set's buffer took: again, into one that takes them
+        HIPCHK(set.own->site_recs.ensure((size_t)c));
+        const int r = launch(set, rows, start, cnt);
+        if (r) return r;
         HIPCHK(hipStreamSynchronize(set.st));
       }
       raw.resize((size_t)c);
-      HIPCHK(hipMemcpyAsync(raw.data(), h->site_recs[si].p, (size_t)c * sizeof(SiteRec), hipMemcpyDeviceToHost, set.st));
+      HIPCHK(hipMemcpyAsync(raw.data(), set.own->site_recs.p, (size_t)c * sizeof(SiteRec), hipMemcpyDeviceToHost, set.st));
       HIPCHK(hipStreamSynchronize(set.st));
-      sort_sites(raw, prev_cnt, &sorted);
+      sort_sites(raw, cnt, &sorted);
       const size_t keep = (size_t)std::min<int64_t>((int64_t)c, capacity - total);
       for (size_t r = 0; r < keep; ++r) {
         const SiteRec& x = sorted[r];
-        sites[total + (int64_t)r] = crbm_site{x.seq + prev_start, x.motif, x.start, x.strand, x.prob};
+        sites[total + (int64_t)r] = crbm_site{x.seq + start, x.motif, x.start, x.strand, x.prob};
       }
     }
     total += (int64_t)c;
     if (want_best) {
       for (size_t r = 0; r < keys.size(); ++r) {
-        const size_t o = (size_t)prev_start * K + r;
+        const size_t o = (size_t)start * K + r;
         const uint32_t code = 0xFFFFFFFFu - (uint32_t)keys[r];
         float p;
         const uint32_t bits = (uint32_t)(keys[r] >> 32);
@@ -2722,34 +2700,20 @@ int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64
     }
     return CRBM_OK;
   };
-  for (int start = 0, i = 0; start < n; start += slab, ++i) {
-    const int cnt = std::min(slab, n - start);
-    const SweepSet set = sweep_set(h, i);
-    const uint32_t* rows = nullptr;
-    rc = sweep_rows(h, src, start, cnt, set, &rows);
-    if (rc) return rc;
-    rc = launch(i, rows, cnt);
-    if (rc) return rc;
-    rc = collect();
-    if (rc) return rc;
-    prev_i = i; prev_start = start; prev_cnt = cnt; prev_rows = rows;
-  }
-  rc = collect();
-  if (rc) return rc;
-  rc = sweep_finish(h, src);
+  rc = sweep_run(h, src, slab, 2, launch, collect);
   if (rc) return rc;
   if (count) *count = want_recs ? total : 0;
   return CRBM_OK;
 }
 
 // ---- in-silico mutagenesis (crbm_mutagenesis*) ----------------------------------------------------------------------
-// dF (n,L,A) and / or pll (n) over a source, slab by slab on the two streams of a sweep.  Specialised models without
-// pooling: the fused crbm_mutagenesis pass (mutagenesis_body; as many waves per block as the LDS holds accumulators
-// beside the tables).  Everything else -- pooled models, generic models, CRBM_MUT_FUSED=0, sequences whose accumulator
-// does not fit beside the tables -- takes the general path: mutagenesis_expand_kernel writes the slab's base rows and
-// their (A-1) L copies, the class's own free-energy launch (launch_free_energy) leaves their per-motif terms in the
-// set's outputs, mutagenesis_combine_kernel forms dF and pll.  Every set owns what it writes, sized before the loop;
-// the slab comes from the slab budget with the copies, their free energies and the outputs counted per row.
+// dF (n,L,A) and / or pll (n) over a source, a two-stream sweep.  Specialised models without pooling: the fused
+// crbm_mutagenesis pass (mutagenesis_body; as many waves per block as the LDS holds accumulators beside the tables).
+// Everything else -- pooled models, generic models, CRBM_MUT_FUSED=0, sequences whose accumulator does not fit beside
+// the tables -- takes the general path: mutagenesis_expand_kernel writes the slab's base rows and their (A-1) L copies,
+// the class's own free-energy launch (launch_free_energy) leaves their per-motif terms in the set's outputs,
+// mutagenesis_combine_kernel forms dF and pll.  Every set owns what it writes, sized before the sweep; the slab comes
+// from the slab budget with the copies, their free energies and the outputs counted per row.
 int mutagenesis_any(crbm_handle* h, const RowSource& src, float* dfe, float* pll) {
   ARGCHK(dfe || pll, "null argument");
   int rc = check_data_shape(h, src.n, src.L);
@@ -2777,79 +2741,55 @@ int mutagenesis_any(crbm_handle* h, const RowSource& src, float* dfe, float* pll
   if (!fused) slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)slab, ((size_t)1 << 30) / per));   // expanded rows are counted in int
   // slabs of equal size: the two streams' launches run side by side, a short last slab would leave one of them idle
   if (slab < n) slab = (n + (n + slab - 1) / slab - 1) / ((n + slab - 1) / slab);
-  const int nsets = slab < n ? 2 : 1;
-  for (int i = 0; i < nsets; ++i) {        // everything both streams write, at its size, before either starts
+  for (int i = 0; i < (slab < n ? 2 : 1); ++i) {        // everything both streams write, at its size, before either starts
     const SweepSet set = sweep_set(h, i);
-    HIPCHK(h->mut_pll[i].ensure((size_t)slab));
-    if (dfe) HIPCHK(h->mut_df[i].ensure((size_t)slab * L * A));
+    HIPCHK(set.own->mut_pll.ensure((size_t)slab));
+    if (dfe) HIPCHK(set.own->mut_df.ensure((size_t)slab * L * A));
     if (!fused) {
-      HIPCHK(h->mut_rows[i].ensure((size_t)slab * per * LW));
+      HIPCHK(set.own->mut_rows.ensure((size_t)slab * per * LW));
       HIPCHK(set.oa->ensure((size_t)slab * per));
       HIPCHK(set.ob->ensure((size_t)slab * per * K));
       if (slabbed_fe) HIPCHK(set.fe_scratch->ensure((size_t)slab * per * h->slab->K * h->slab_n));
     }
   }
-  auto launch = [&](int i, const uint32_t* rows, int cnt) -> int {
-    const SweepSet set = sweep_set(h, i & 1);
-    float* d_df = dfe ? h->mut_df[i & 1].p : nullptr;
-    float* d_pll = h->mut_pll[i & 1].p;
-    if (fused) {
-      MutArgs a;
-      a.tables = h->d_tables; a.letters = rows;
-      a.n = cnt; a.L = L; a.Lh = L - h->M + 1; a.LW = LW;
-      a.dfe = d_df; a.pll = d_pll;
-      // num_cu * 8 blocks like the other sweep kernels; a grid of only the resident blocks (5 per CU at config #2: no
-      // second table copy) measured no faster, 8.70 against 8.46 ms over 10^5 x 200 bp: the kernel is bound by its VALU work
-      const unsigned gx = (unsigned)std::max(1, std::min((cnt + waves - 1) / waves, h->num_cu * 8));
-      HIPCHK(jit_launch(h->jk.mutagenesis, a, gx, 1, 64u * (unsigned)waves, lds, set.st));
+  return sweep_run(h, src, slab, 2,
+    [&](const SweepSet& set, const uint32_t* rows, int, int cnt) -> int {
+      float* d_df = dfe ? set.own->mut_df.p : nullptr;
+      float* d_pll = set.own->mut_pll.p;
+      if (fused) {
+        MutArgs a;
+        a.tables = h->d_tables; a.letters = rows;
+        a.n = cnt; a.L = L; a.Lh = L - h->M + 1; a.LW = LW;
+        a.dfe = d_df; a.pll = d_pll;
+        // num_cu * 8 blocks like the other sweep kernels; a grid of only the resident blocks (5 per CU at config #2: no
+        // second table copy) measured no faster, 8.70 against 8.46 ms over 10^5 x 200 bp: the kernel is bound by its VALU work
+        const unsigned gx = (unsigned)std::max(1, std::min((cnt + waves - 1) / waves, h->num_cu * 8));
+        HIPCHK(jit_launch(h->jk.mutagenesis, a, gx, 1, 64u * (unsigned)waves, lds, set.st));
+        return CRBM_OK;
+      }
+      const size_t R = (size_t)cnt * per;
+      MutExpandArgs e;
+      e.rows = rows; e.out = set.own->mut_rows.p;
+      e.n = cnt; e.L = L; e.LW = LW; e.A = A;
+      hipLaunchKernelGGL(mutagenesis_expand_kernel, dim3(grid_for((long)(R * LW), 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
+      HIPCHK(hipGetLastError());
+      const int r = launch_free_energy(h, e.out, (int)R, L, set);
+      if (r) return r;
+      MutCombineArgs c;
+      c.fem = set.ob->p; c.c = h->dc; c.rows = rows;
+      c.n = cnt; c.L = L; c.LW = LW; c.A = A; c.K = K;
+      c.dfe = d_df; c.pll = d_pll;
+      hipLaunchKernelGGL(mutagenesis_combine_kernel, dim3(std::max(1, std::min((cnt + 3) / 4, h->num_cu * 8))), dim3(256), 0, set.st, c);
+      HIPCHK(hipGetLastError());
       return CRBM_OK;
-    }
-    const size_t R = (size_t)cnt * per;
-    MutExpandArgs e;
-    e.rows = rows; e.out = h->mut_rows[i & 1].p;
-    e.n = cnt; e.L = L; e.LW = LW; e.A = A;
-    hipLaunchKernelGGL(mutagenesis_expand_kernel, dim3(grid_for((long)(R * LW), 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
-    HIPCHK(hipGetLastError());
-    int r = launch_free_energy(h, e.out, (int)R, L, set);
-    if (r) return r;
-    MutCombineArgs c;
-    c.fem = set.ob->p; c.c = h->dc; c.rows = rows;
-    c.n = cnt; c.L = L; c.LW = LW; c.A = A; c.K = K;
-    c.dfe = d_df; c.pll = d_pll;
-    hipLaunchKernelGGL(mutagenesis_combine_kernel, dim3(std::max(1, std::min((cnt + 3) / 4, h->num_cu * 8))), dim3(256), 0, set.st, c);
-    HIPCHK(hipGetLastError());
-    return CRBM_OK;
-  };
-  int prev_i = -1, prev_start = 0, prev_cnt = 0;
-  auto collect = [&]() -> int {     // outputs of the previous slab -> host
-    if (prev_i < 0) return CRBM_OK;
-    const SweepSet set = sweep_set(h, prev_i & 1);
-    if (dfe) HIPCHK(hipMemcpyAsync(dfe + (size_t)prev_start * L * A, h->mut_df[prev_i & 1].p, (size_t)prev_cnt * L * A * sizeof(float), hipMemcpyDeviceToHost, set.st));
-    if (pll) HIPCHK(hipMemcpyAsync(pll + prev_start, h->mut_pll[prev_i & 1].p, (size_t)prev_cnt * sizeof(float), hipMemcpyDeviceToHost, set.st));
-    HIPCHK(hipStreamSynchronize(set.st));
-    return CRBM_OK;
-  };
-  for (int start = 0, i = 0; start < n; start += slab, ++i) {
-    const int cnt = std::min(slab, n - start);
-    const SweepSet set = sweep_set(h, i);
-    const uint32_t* rows = nullptr;
-    rc = sweep_rows(h, src, start, cnt, set, &rows);
-    if (rc) return rc;
-    rc = launch(i, rows, cnt);
-    if (rc) return rc;
-    rc = collect();
-    if (rc) return rc;
-    prev_i = i; prev_start = start; prev_cnt = cnt;
-  }
-  rc = collect();
-  if (rc) return rc;
-  return sweep_finish(h, src);
+    },
+    [&](const SweepSet& set, const uint32_t*, int start, int cnt) -> int {
+      if (dfe) HIPCHK(hipMemcpyAsync(dfe + (size_t)start * L * A, set.own->mut_df.p, (size_t)cnt * L * A * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      if (pll) HIPCHK(hipMemcpyAsync(pll + start, set.own->mut_pll.p, (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      HIPCHK(hipStreamSynchronize(set.st));
+      return CRBM_OK;
+    });
 }
-
-static RowSource host_onehot_(const float* v, int n, int L, int A) { RowSource s; s.onehot = v; s.n = n; s.L = L; s.A = A; return s; }
-static RowSource host_codes_(const uint8_t* c, int n, int L, int A) { RowSource s; s.codes = c; s.n = n; s.L = L; s.A = A; return s; }
-#define host_onehot(v, n, L) host_onehot_(v, n, L, h->A)
-#define host_codes(c, n, L) host_codes_(c, n, L, h->A)
 
 }  // namespace
 
@@ -3271,8 +3211,7 @@ int crbm_train_local(crbm_handle* h, const float* D, int32_t n, int32_t L, float
   if (rc) return rc;
   ARGCHK(n >= 0, "n must be non-negative");
   if (n > 0) {   // n == 0: a rank that owns no row of a short last mini-batch contributes zeros
-    HIPCHK(h->letters.ensure((size_t)n * lw(h, L)));
-    rc = encode_host(h, D, n, L, h->letters.p);
+    rc = encode_now(h, host_onehot(D, n, L), 0, n);
     if (rc) return rc;
   }
   rc = train_local_dev(h, h->letters.p, n, L);
