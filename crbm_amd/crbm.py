@@ -482,6 +482,92 @@ class CRBM(object):
             out[f] = raw[f]
         return out
 
+    _SCAN_MAX = 2 ** 31 - 1          # letters one crbm_scan_sites_codes call takes (start is 32 bits wide)
+
+    def _scan_input(self, stream, threshold, offsets):
+        """the argument checks of scanSites, before any C call: (threshold, stream, offsets or None)"""
+        t = self._threshold(threshold)
+        if not isinstance(stream, np.ndarray) or stream.dtype != np.uint8:
+            raise ValueError("stream must be a uint8 array of codes 0..4 (sequences.seqsToStream)")
+        if stream.ndim != 1:
+            raise ValueError("stream must be one-dimensional, got shape %r" % (stream.shape,))
+        stream = np.ascontiguousarray(stream)
+        if stream.size and int(stream.max()) > 4:
+            raise ValueError("stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)")
+        if offsets is not None:
+            offsets = np.asarray(offsets)
+            if offsets.ndim != 1 or offsets.size < 1 or not np.issubdtype(offsets.dtype, np.integer):
+                raise ValueError("offsets must be a 1-D integer array of record starts (sequences.seqsToStream)")
+            offsets = offsets.astype(np.int64)
+            if offsets[0] != 0 or np.any(np.diff(offsets) < 1):
+                raise ValueError("offsets must start at 0 and ascend (every record is followed by one separator)")
+            if offsets.size > 1 and offsets[-1] != stream.size + 1:
+                raise ValueError("offsets do not fit the stream: the last entry must be len(stream) + 1")
+            if offsets.size == 1 and stream.size:
+                raise ValueError("offsets do not fit the stream: no records, but letters")
+            if offsets.size > 2 and np.any(stream[offsets[1:-1] - 1] != 4):
+                raise ValueError("offsets do not fit the stream: records must be separated by a code 4")
+        return t, stream, offsets
+
+    def _scan_call(self, stream, t):
+        """crbm_scan_sites_codes over one piece of at most _SCAN_MAX letters: raw records"""
+        count = ctypes.c_int64(0)
+
+        def call(capacity):
+            raw = np.empty(capacity, dtype=_RAW_SITE)
+            self._call("crbm_scan_sites_codes", stream.ctypes.data_as(_lib._U8P), stream.size, t, capacity,
+                       raw.ctypes.data_as(ctypes.POINTER(_lib.CrbmSite)), ctypes.byref(count))
+            return raw
+        capacity = int(min(max(stream.size, 1) * self.num_motifs * 2, max(1 << 20, stream.size // 16)))
+        raw = call(capacity)
+        if count.value > capacity:
+            raw = call(count.value)          # more sites than the first buffer took: the scan is computed again
+        return raw[:count.value]
+
+    def scanSites(self, stream, threshold=0.5, offsets=None):
+        """motifSites for whole records of any length: `stream` is a 1-D uint8 array of codes, 0..3 = A,C,G,T and
+        4 = no letter (N, ambiguity codes, record separators) -- sequences.seqsToStream / fastaToStream make it.  Every
+        window of motif_length letters is scored as motifSites scores the same letters in a row (the same bits); a
+        window that touches a code 4 yields nothing.  Returns SITE_DTYPE records.  Without `offsets`: seq 0, start the
+        stream position, sorted by (start, motif, strand).  With the `offsets` of seqsToStream: seq the record index,
+        start relative to the record, sorted by (seq, start, motif, strand), + before - -- saveSites(model, sites,
+        "x.bed", names=names) writes them as BED.  Models with pooling, other alphabets or motifs beyond 64 letters are
+        refused."""
+        t, stream, offsets = self._scan_input(stream, threshold, offsets)
+        pieces, lo = [], 0
+        while True:                          # pieces of at most _SCAN_MAX letters, cut at record boundaries
+            hi = stream.size
+            if hi - lo > self._SCAN_MAX:
+                if offsets is None:
+                    raise ValueError("a stream of more than 2^31 - 1 letters needs offsets (it is cut at record boundaries)")
+                i = int(np.searchsorted(offsets, lo + self._SCAN_MAX + 1, side="right")) - 1
+                hi = int(offsets[i]) - 1     # the separator in front of record i: the piece ends with the record before
+                if hi <= lo:
+                    raise ValueError("a record of more than 2^31 - 1 letters cannot be scanned")
+            raw = self._scan_call(stream[lo:hi], t)
+            pieces.append((lo, raw))
+            if hi >= stream.size:
+                break
+            lo = hi + 1
+        n = sum(r.size for _, r in pieces)
+        out = np.empty(n, dtype=self.SITE_DTYPE)
+        pos = np.empty(n, dtype=np.int64)
+        at = 0
+        for lo, raw in pieces:
+            sl = slice(at, at + raw.size)
+            for f in ("motif", "strand", "prob"):
+                out[f][sl] = raw[f]
+            pos[sl] = raw["start"].astype(np.int64) + lo
+            at += raw.size
+        if offsets is None:
+            out["seq"] = 0
+            out["start"] = pos
+        else:
+            seq = np.searchsorted(offsets, pos, side="right") - 1
+            out["seq"] = seq
+            out["start"] = pos - offsets[seq]
+        return out
+
     def motifBestSites(self, data):
         """The best site of every (sequence, motif): dict of 'start' (n,K) int32, 'strand' (n,K) int8 and
         'prob' (n,K) float32 -- the largest probability over positions and strands (motifSites' scores),

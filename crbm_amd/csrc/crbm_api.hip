@@ -16,6 +16,7 @@
 #include <deque>
 #include <mutex>
 #include <thread>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -175,6 +176,10 @@ struct crbm_handle {
     DevBuf<unsigned long long> site_count, site_keys;
     DevBuf<float> mut_df, mut_pll;
     DevBuf<uint32_t> mut_rows;
+    // stream scan: validity plane of the segment, per-lane and per-tile hit counts, tile offsets and (behind them) the totals
+    DevBuf<unsigned long long> scan_valid, scan_off;
+    DevBuf<unsigned short> scan_lanes;
+    DevBuf<uint32_t> scan_tiles;
   } set_bufs[2];
   int mut_route = 0;                               // route of the last crbm_mutagenesis* call: 1 fused kernel, 2 general path
   // annealed importance sampling (crbm_ais): the ladder, cA, the runs' log weights and letter codes between launches
@@ -1905,6 +1910,7 @@ int crbm_destroy(crbm_handle* h) {
   for (auto& d : h->dataset) d.release(); h->partials.release(); h->partials2.release();
   for (auto& b : h->set_bufs) {
     b.site_recs.release(); b.site_count.release(); b.site_keys.release();
+    b.scan_valid.release(); b.scan_off.release(); b.scan_lanes.release(); b.scan_tiles.release();
     b.mut_df.release(); b.mut_pll.release(); b.mut_rows.release();
   }
   h->ais_betas.release(); h->ais_base.release(); h->ais_logw.release(); h->ais_state.release();
@@ -2706,6 +2712,179 @@ int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64
   return CRBM_OK;
 }
 
+// ---- stream scan (crbm_scan_sites_codes) ---------------------------------------------------------------------------
+// The sites of a stream of T codes (0..3 letters, 4 no letter), a two-stream sweep over segments of window starts:
+// segment [start, start + cnt) needs letters [start, start + cnt + M - 1), a halo of M - 1 behind its own.  Per segment
+// on the set's stream: the bytes go up (one per letter), scan_encode_kernel makes letters and validity plane,
+// crbm_scan_sites counts (pass 0), scan_offsets_kernel scans the tile counts, crbm_scan_sites writes the records at
+// their offsets (pass 1) -- in final order, so that a model on its own kernels is copied straight into the caller's
+// array.  A generic DNA model runs the kernel of its slab model, blockIdx.y = slab, every slab with its own counts,
+// offsets and records; the slabs' runs, each sorted by start and owning ascending motifs, are merged on the host by
+// (start, slab).  Every set owns what it writes, sized for a whole segment before the sweep starts; only the records
+// may have to grow, as in motif_sites_any: pass 1 is then run again before anything is copied.  Since records are in
+// final order, a segment needs no more room than what the caller's capacity still takes.
+int scan_sites_any(crbm_handle* h, const uint8_t* codes, int64_t T, float threshold, int64_t capacity, crbm_site* sites,
+                   int64_t* count) {
+  ARGCHK(count, "null argument");
+  ARGCHK(threshold >= 0.f && threshold <= 1.f, "threshold must lie in [0, 1]");   // (NaN fails both)
+  ARGCHK(capacity >= 0, "capacity must be >= 0");
+  ARGCHK(sites || capacity == 0, "sites is required with a capacity");
+  ARGCHK(T >= 0 && T <= (int64_t)INT32_MAX, "stream length must lie in [0, 2^31 - 1] (start is 32 bits wide)");
+  ARGCHK(codes || T == 0, "null argument");
+  ARGCHK(h->A == 4, "crbm_scan_sites_codes: the alphabet must be DNA's (input_dims == 4)");
+  ARGCHK(h->ms.POOL == 1, "crbm_scan_sites_codes: pooling > 1 is not supported (pool groups have no anchor in a stream)");
+  crbm_handle* km = h->big ? h->slab : h;          // whose kernel runs: the model's own, or that of its slab model
+  ARGCHK(km && tab_bytes(km) <= 160 * 1024, "crbm_scan_sites_codes: models that run on the generic kernels alone (motifs beyond 64 letters) are not supported");
+  *count = 0;
+  const int M = h->M, S = h->ds ? 2 : 1;
+  if (T < M) return CRBM_OK;
+  const int starts_all = (int)(T - M + 1), nslab = h->big ? h->slab_n : 1;
+  int rc = sweep_begin(h);
+  if (rc) return rc;
+  // a window start costs its staged byte, its letter and validity bits, per slab its counts and offsets, and a share of records
+  const size_t per_start = 4 + (size_t)4 * nslab;
+  int seg = slab_rows(starts_all, per_start);
+  if (!getenv("CRBM_SLAB_BYTES")) seg = (int)std::min<size_t>((size_t)seg, std::max<size_t>(1, (32u << 20) / per_start));
+  const bool want_recs = capacity > 0;
+  const ScanLayout lay = scan_layout((long)seg + M - 1, seg);
+  size_t rcap[2] = {0, 0};                               // records per slab a set's buffer is used for
+  const int nsets = seg < starts_all ? 2 : 1;
+  for (int i = 0; i < nsets; ++i) {                      // everything both streams write, at its size, before either starts
+    const SweepSet set = sweep_set(h, i);
+    HIPCHK(set.stage->ensure(((size_t)seg + M - 1 + 3) / 4));
+    HIPCHK(set.letters->ensure((size_t)lay.letter_words));
+    HIPCHK(set.own->scan_valid.ensure((size_t)lay.valid_words));
+    HIPCHK(set.own->scan_lanes.ensure((size_t)nslab * 64 * lay.tiles));
+    HIPCHK(set.own->scan_tiles.ensure((size_t)nslab * lay.tiles));
+    HIPCHK(set.own->scan_off.ensure((size_t)nslab * lay.tiles + nslab));
+    if (want_recs) {
+      rcap[i] = (size_t)std::min<unsigned long long>({(unsigned long long)capacity, (unsigned long long)seg * km->K * S,
+                                                     std::max<unsigned long long>(1ull << 16, (unsigned long long)seg / 4)});
+      HIPCHK(set.own->site_recs.ensure(rcap[i] * nslab));
+    }
+  }
+  auto scan_args = [&](const SweepSet& set, int si, int start, int cnt, int pass) {
+    const ScanLayout l = scan_layout((long)cnt + M - 1, cnt);
+    ScanArgs a;
+    a.tables = h->big ? h->d_slab_tables : h->d_tables;
+    a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
+    a.lane_cnt = set.own->scan_lanes.p; a.tile_cnt = set.own->scan_tiles.p; a.tile_off = set.own->scan_off.p;
+    a.recs = set.own->site_recs.p; a.capacity = rcap[si];
+    a.starts = cnt; a.tiles = l.tiles; a.pos0 = start; a.pass = pass; a.threshold = threshold;
+    a.table_stride = km->ms.TABLES_ALL;
+    if (h->big) a.plan = slab_plan(h);
+    else { a.plan.Ks = h->K; a.plan.K = h->K; a.plan.last_k0 = 0; }
+    return a;
+  };
+  auto launch_pass = [&](const SweepSet& set, int si, int start, int cnt, int pass) -> int {
+    const ScanArgs a = scan_args(set, si, start, cnt, pass);
+    const unsigned gx = (unsigned)std::max(1, std::min((a.tiles + 3) / 4, std::max(1, h->num_cu * 8 / nslab)));
+    HIPCHK(jit_launch(km->jk.scan_sites, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(km), set.st));
+    return CRBM_OK;
+  };
+  int64_t total = 0;
+  bool wrote[2] = {false, false};                        // the set's segment went through pass 1
+  // CRBM_SCAN_TIMING=1 (tools/bench_scan.py): events around every segment's kernels, their sum on stderr
+  const bool timing = env_int("CRBM_SCAN_TIMING", 0) != 0;
+  hipEvent_t tev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  double device_ms = 0.0;
+  int segments = 0;
+  if (timing)
+    for (int i = 0; i < 2; ++i)
+      for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
+  std::vector<unsigned long long> tot((size_t)nslab);
+  std::vector<std::vector<SiteRec>> runs((size_t)(nslab > 1 ? nslab : 0));
+  rc = run_slabs(starts_all, seg, 2,
+    [&](int, int si, int start, int cnt) -> int {
+      const SweepSet set = sweep_set(h, si);
+      const long n = (long)cnt + M - 1;                  // (start + cnt <= T - M + 1: the halo is inside the stream)
+      const ScanLayout l = scan_layout(n, cnt);
+      HIPCHK(hipMemcpyAsync(set.stage->p, codes + start, (size_t)n, hipMemcpyHostToDevice, set.st));
+      if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
+      ScanEncodeArgs e;
+      e.codes = reinterpret_cast<const unsigned char*>(set.stage->p);
+      e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;
+      e.n = n; e.valid_words = l.valid_words;
+      hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
+      HIPCHK(hipGetLastError());
+      int r = launch_pass(set, si, start, cnt, 0);
+      if (r) return r;
+      ScanOffsetsArgs o;
+      o.tile_cnt = set.own->scan_tiles.p; o.tile_off = set.own->scan_off.p;
+      o.total = set.own->scan_off.p + (size_t)nslab * l.tiles; o.tiles = l.tiles;
+      hipLaunchKernelGGL(scan_offsets_kernel, dim3(nslab), dim3(1024), 1024 * sizeof(unsigned long long), set.st, o);
+      HIPCHK(hipGetLastError());
+      wrote[si] = want_recs && total < capacity;         // (`total` lags by one segment and only grows: never skipped wrongly)
+      r = wrote[si] ? launch_pass(set, si, start, cnt, 1) : CRBM_OK;
+      if (!r && timing) HIPCHK(hipEventRecord(tev[si][1], set.st));
+      return r;
+    },
+    [&](int, int si, int start, int cnt) -> int {
+      const SweepSet set = sweep_set(h, si);
+      const ScanLayout l = scan_layout((long)cnt + M - 1, cnt);
+      HIPCHK(hipMemcpyAsync(tot.data(), set.own->scan_off.p + (size_t)nslab * l.tiles, (size_t)nslab * 8, hipMemcpyDeviceToHost, set.st));
+      HIPCHK(hipStreamSynchronize(set.st));
+      if (timing) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, tev[si][0], tev[si][1]));
+        device_ms += ms;
+        ++segments;
+      }
+      unsigned long long c = 0, most = 0;
+      for (int y = 0; y < nslab; ++y) c += tot[y];
+      if (wrote[si] && total < capacity && c > 0) {
+        const unsigned long long keep = std::min<unsigned long long>(c, (unsigned long long)(capacity - total));
+        for (int y = 0; y < nslab; ++y) most = std::max(most, std::min(tot[y], keep));
+        if (most > rcap[si]) {        // more records than the set's buffer took: pass 1 again, into one that takes them
+          HIPCHK(set.own->site_recs.ensure((size_t)most * nslab));
+          rcap[si] = (size_t)most;
+          const int r = launch_pass(set, si, start, cnt, 1);
+          if (r) return r;
+        }
+        if (nslab == 1) {
+          HIPCHK(hipMemcpyAsync(sites + total, set.own->site_recs.p, (size_t)keep * sizeof(SiteRec), hipMemcpyDeviceToHost, set.st));
+          HIPCHK(hipStreamSynchronize(set.st));
+        } else {
+          for (int y = 0; y < nslab; ++y) {
+            runs[y].resize((size_t)std::min(tot[y], keep));
+            if (!runs[y].empty())
+              HIPCHK(hipMemcpyAsync(runs[y].data(), set.own->site_recs.p + (size_t)y * rcap[si], runs[y].size() * sizeof(SiteRec), hipMemcpyDeviceToHost, set.st));
+          }
+          HIPCHK(hipStreamSynchronize(set.st));
+          std::vector<size_t> at((size_t)nslab, 0);
+          for (unsigned long long r = 0; r < keep; ++r) {       // the smallest start, then the lowest slab: (start, motif, strand)
+            int best = -1;
+            for (int y = 0; y < nslab; ++y)
+              if (at[y] < runs[y].size() && (best < 0 || runs[y][at[y]].start < runs[best][at[best]].start)) best = y;
+            const SiteRec& x = runs[best][at[best]++];
+            sites[total + (int64_t)r] = crbm_site{x.seq, x.motif, x.start, x.strand, x.prob};
+          }
+        }
+      }
+      total += (int64_t)c;
+      return CRBM_OK;
+    },
+    [&] { sweep_drain(h); });
+  if (timing) {
+    for (int i = 0; i < 2; ++i)
+      for (int j = 0; j < 2; ++j) (void)hipEventDestroy(tev[i][j]);
+    if (!rc) fprintf(stderr, "crbm_scan_sites_codes: kernels %.3f ms over %d segments\n", device_ms, segments);
+  }
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream2));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  uint32_t flags = 0;
+  HIPCHK(hipMemcpyAsync(&flags, h->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (flags) {
+    HIPCHK(hipMemsetAsync(h->d_flags, 0, sizeof(uint32_t), h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return fail(h, CRBM_ERR_INVALID, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
+  }
+  *count = total;
+  return CRBM_OK;
+}
+
 // ---- in-silico mutagenesis (crbm_mutagenesis*) ----------------------------------------------------------------------
 // dF (n,L,A) and / or pll (n) over a source, a two-stream sweep.  Specialised models without pooling: the fused
 // crbm_mutagenesis pass (mutagenesis_body; as many waves per block as the LDS holds accumulators beside the tables).
@@ -2948,6 +3127,12 @@ int crbm_motif_sites_resident(crbm_handle* h, int32_t start, int32_t end, float 
   int rc = resident_source(h, start, end, &src);
   if (rc) return rc;
   return motif_sites_any(h, src, threshold, capacity, sites, count, best_start, best_strand, best_prob);
+}
+
+int crbm_scan_sites_codes(crbm_handle* h, const uint8_t* codes, int64_t T, float threshold, int64_t capacity,
+                          crbm_site* sites, int64_t* count) {
+  ENTER();
+  return scan_sites_any(h, codes, T, threshold, capacity, sites, count);
 }
 
 int crbm_mutagenesis(crbm_handle* h, const float* v, int32_t n, int32_t L, float* dfe, float* pll) {

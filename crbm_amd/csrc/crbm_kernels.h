@@ -2921,6 +2921,135 @@ __device__ void slab_fe_body(const SlabFeArgs& s) {
   free_energy_body<C>(a);
 }
 
+// ===========================================================================
+// Stream scan (crbm_scan_sites_codes): the sites of a 1-D stream of letters in which some positions hold no letter.
+// A window [s, s + M) is valid when all of its M positions hold letters; a valid window scores exactly like the same
+// M letters in a row of motif_sites_body (the same gather calls in the same order: the same bits); an invalid one
+// yields nothing.  The segment arrives as 2-bit letter words and a validity plane (crbm_layout.h, scan_layout;
+// scan_encode_kernel).  A block keeps the gather table in LDS; a wave walks tiles of 64 window starts, a lane owns one.
+// Records leave the device in their final order -- (start, motif, strand), + before - -- in two passes of this body:
+//   pass 0  a lane counts its hits over all motifs and strands (lane_cnt) and the wave adds the counts up (tile_cnt);
+//           scan_offsets_kernel then turns the tile counts into exclusive offsets and the total;
+//   pass 1  the waves of tiles that have hits score them again; a lane writes its records one after the other from
+//           tile offset + (counts of the lower lanes) on, those below `capacity`.
+// No reservation atomics, no float combined across threads: the same bits in every run and for every geometry.
+// blockIdx.y is the slab of a generic DNA model (its table image, its motifs [k0 + kskip, min(k0 + Ks, K)), its part of
+// every buffer); a model on its own kernels is one slab of all its motifs.
+// ===========================================================================
+struct ScanArgs {
+  const float* tables;                 // the first slab's image
+  const uint32_t* letters;
+  const unsigned long long* valid;
+  unsigned short* lane_cnt;            // [slab][64 * tiles]
+  uint32_t* tile_cnt;                  // [slab][tiles]
+  const unsigned long long* tile_off;  // [slab][tiles], pass 1
+  SiteRec* recs;                       // [slab][capacity], pass 1
+  unsigned long long capacity;         // records per slab
+  int32_t starts, tiles;               // window starts of the segment, tiles of 64 of them
+  int32_t pos0;                        // stream position of the segment's first letter
+  int32_t pass;
+  float threshold;
+  int32_t table_stride;                // floats
+  SlabPlan plan;
+};
+// sum over the wave and over the lower lanes of a small per-lane count (< 2^BITS), bit plane by bit plane (all lanes call it)
+template <int BITS>
+__device__ __forceinline__ void wave_count_sums(uint32_t c, uint32_t& below, uint32_t& total) {
+  below = 0; total = 0;
+#pragma unroll
+  for (int b = 0; b < BITS; ++b) {
+    const unsigned long long m = __ballot((c >> b) & 1u);
+    below += lanes_below(m) << b;
+    total += (uint32_t)__popcll(m) << b;
+  }
+}
+
+template <class C>
+__device__ void scan_sites_body(const ScanArgs& a) {
+  if constexpr (C::POOL == 1) {       // pool groups have no anchor in a stream: refused on the host, no body
+    constexpr int M = C::M, S = C::DS ? 2 : 1;
+    constexpr int NQW = C::NQ < 4 ? C::NQ : 4, NV = 4 * NQW;
+    constexpr bool BOTH = !C::DS;     // single-stranded models score sigma(x + x'), as motif_sites_body
+    static_assert(C::K * S < (1 << 10), "a lane's count must fit ten bits");
+    HIP_DYNAMIC_SHARED(float, smem);
+    float* Tf = smem;
+    const int y = (int)blockIdx.y, k0 = slab_k0(a.plan, y);
+    const int kskip = y > 0 ? max(0, slab_k0(a.plan, y - 1) + a.plan.Ks - k0) : 0;   // motifs the neighbouring slab reports
+    const int kend = min(C::K, a.plan.K - k0);
+    copy_tables<C::TAB>(Tf, a.tables + (size_t)y * a.table_stride + C::OFF_TF);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const float thr = a.threshold;
+    unsigned short* lane_cnt = a.lane_cnt + (size_t)y * 64 * a.tiles;
+    uint32_t* tile_cnt = a.tile_cnt + (size_t)y * a.tiles;
+    // p[] = the scores of motifs [4 q0, 4 q0 + NV) of the window on `strand`: motif_sites_body's gather, to the instruction
+    auto scores = [&](const LetterWin<M>& w, int q0, int strand, float (&p)[NV]) {
+      float z[NV];
+      conv_gather_quads<C, NQW>(Tf, strand ? revcomp_window<M>(w) : w, q0, z);
+      if (BOTH) conv_gather_quads<C, NQW, true>(Tf, revcomp_window<M>(w), q0, z);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) p[j] = sigmoid_z(z[j]);
+    };
+    auto is_hit = [&](int kk, float p) { return kk >= kskip && kk < kend && p >= thr; };
+    for (int t = blockIdx.x * nwaves + wave; t < a.tiles; t += gridDim.x * nwaves) {
+      const int s = 64 * t + lane;
+      if (a.pass == 0) {
+        bool ok = s < a.starts;
+        if (ok) {                     // all M validity bits from s on
+          const int sh = s & 63;
+          const unsigned long long v0 = a.valid[s >> 6], v1 = a.valid[(s >> 6) + 1];
+          const unsigned long long v = sh ? (v0 >> sh) | (v1 << (64 - sh)) : v0;
+          const unsigned long long need = M < 64 ? (1ull << M) - 1ull : ~0ull;
+          ok = (v & need) == need;
+        }
+        uint32_t c = 0;
+        if (ok) {
+          const LetterWin<M> w = letter_window<M>(a.letters, s);
+#pragma unroll 1
+          for (int q0 = 0; q0 < C::NQ; q0 += NQW)
+#pragma unroll 1
+            for (int strand = 0; strand < S; ++strand) {
+              float p[NV];
+              scores(w, q0, strand, p);
+#pragma unroll
+              for (int j = 0; j < NV; ++j) c += is_hit(4 * q0 + j, p[j]) ? 1u : 0u;
+            }
+        }
+        lane_cnt[s] = (unsigned short)c;   // (the buffer holds whole tiles)
+        uint32_t below, total;
+        wave_count_sums<10>(c, below, total);
+        if (lane == 0) tile_cnt[t] = total;
+      } else {
+        if (tile_cnt[t] == 0) continue;                     // wave-uniform
+        const uint32_t c = lane_cnt[s];
+        uint32_t below, total;
+        wave_count_sums<10>(c, below, total);
+        unsigned long long idx = a.tile_off[(size_t)y * a.tiles + t] + below;
+        SiteRec* recs = a.recs + (size_t)y * a.capacity;
+        const LetterWin<M> w = letter_window<M>(a.letters, s);
+#pragma unroll 1
+        for (int q0 = 0; q0 < (c ? C::NQ : 0); q0 += NQW) {   // lanes without hits sit the tile out
+          float p[S][NV];
+          scores(w, q0, 0, p[0]);
+          if constexpr (S == 2) scores(w, q0, 1, p[1]);
+#pragma unroll
+          for (int j = 0; j < NV; ++j)
+#pragma unroll
+            for (int strand = 0; strand < S; ++strand)
+              if (is_hit(4 * q0 + j, p[strand][j])) {
+                if (idx < a.capacity) {
+                  SiteRec* d = recs + idx;
+                  d->seq = 0; d->motif = k0 + 4 * q0 + j; d->start = a.pos0 + s;
+                  d->strand = C::DS ? (strand ? -1 : 1) : 0; d->prob = p[strand][j];
+                }
+                ++idx;
+              }
+        }
+      }
+    }
+  }
+}
+
 #ifdef CRBM_DEFINE_MISC_KERNELS
 // ===========================================================================
 // Model-independent kernels, compiled ahead of time into libcrbm_hip.so.
@@ -3051,6 +3180,81 @@ __global__ void encode_codes_any_kernel(EncodeCodesArgs a) {
     a.letters[i] = word;
     if (bad) atomicOr(a.flags, 1u);
   }
+}
+
+// A segment of a stream (crbm_scan_sites_codes: codes 0..3 letters, 4 no letter) -> the validity plane and the letter
+// words of scan_layout (crbm_layout.h), letter 0 under every invalid position.  A thread builds one validity word and
+// its four letter words, those of the zero padding too: nothing else initialises the buffers.  flags[0] |= 1 on a code
+// above 4.  `codes` is 4-byte aligned.
+struct ScanEncodeArgs {
+  const unsigned char* codes;   // [n]
+  uint32_t* letters;
+  unsigned long long* valid;
+  uint32_t* flags;
+  long long n, valid_words;
+};
+__global__ void scan_encode_kernel(ScanEncodeArgs a) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.valid_words; i += (long long)gridDim.x * blockDim.x) {
+    unsigned long long v = 0ull;
+    bool bad = false;
+    const long long p0 = 64 * i;
+#pragma unroll 1
+    for (int w = 0; w < 4; ++w) {
+      uint32_t word = 0;
+      for (int q = 0; q < 4; ++q) {
+        const long long p = p0 + 16 * w + 4 * q;
+        uint32_t four = 0x04040404u;                         // past the end: no letters
+        if (p + 4 <= a.n) four = *reinterpret_cast<const uint32_t*>(a.codes + p);
+        else
+          for (int t = 0; t < 4; ++t)
+            if (p + t < a.n) four = (four & ~(0xFFu << (8 * t))) | ((uint32_t)a.codes[p + t] << (8 * t));
+        for (int t = 0; t < 4; ++t) {
+          const uint32_t c = (four >> (8 * t)) & 0xFFu;
+          bad |= c > 4u;
+          if (c < 4u) {
+            word |= c << (2 * (4 * q + t));
+            v |= 1ull << (16 * w + 4 * q + t);
+          }
+        }
+      }
+      a.letters[4 * i + w] = word;
+    }
+    a.valid[i] = v;
+    if (bad) atomicOr(a.flags, 1u);
+  }
+}
+
+// The tail of pass 0 of the stream scan: tile counts -> exclusive offsets and their total, one block per slab
+// (blockIdx.x); a thread sums a run of tiles, the block scans the run sums in LDS (8 bytes per thread, dynamic).
+struct ScanOffsetsArgs {
+  const uint32_t* tile_cnt;        // [slab][tiles]
+  unsigned long long* tile_off;    // [slab][tiles]
+  unsigned long long* total;       // [slab]
+  int32_t tiles;
+};
+__global__ void __launch_bounds__(1024) scan_offsets_kernel(ScanOffsetsArgs a) {
+  HIP_DYNAMIC_SHARED(unsigned long long, part);
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  const uint32_t* cnt = a.tile_cnt + (size_t)blockIdx.x * a.tiles;
+  unsigned long long* off = a.tile_off + (size_t)blockIdx.x * a.tiles;
+  const int run = (a.tiles + nt - 1) / nt;
+  const int lo = (int)min((long long)tid * run, (long long)a.tiles), hi = min(lo + run, a.tiles);
+  unsigned long long sum = 0ull;
+  for (int i = lo; i < hi; ++i) sum += cnt[i];
+  part[tid] = sum;
+  __syncthreads();
+  for (int d = 1; d < nt; d <<= 1) {
+    const unsigned long long add = tid >= d ? part[tid - d] : 0ull;
+    __syncthreads();
+    part[tid] += add;
+    __syncthreads();
+  }
+  unsigned long long at = part[tid] - sum;
+  for (int i = lo; i < hi; ++i) {
+    off[i] = at;
+    at += cnt[i];
+  }
+  if (tid == nt - 1) a.total[blockIdx.x] = part[tid];
 }
 
 // packed letters -> one-hot fp32 (n,1,4,L)

@@ -44,6 +44,21 @@ inline int letter_words(int L) { return (L + 15) / 16 + 2; }
 inline int letter_words_any(int A, int L) { return A == 4 ? letter_words(L) : (L + 3) / 4 + 2; }
 // Mutagenesis kernel (crbm_kernels.h, mutagenesis_body): floats per plane of a wave's LDS accumulator, three planes per wave
 constexpr int mut_plane(int L) { return (L + 63) & ~63; }
+// Stream scan (crbm_kernels.h, scan_sites_body): a segment of n letters lives on the device as a validity plane, one
+// bit per position in 64-bit words with two zero words behind (a lane reads the word of its position and the next one),
+// and as 2-bit letter words, four per validity word (letter 0 under every invalid position; a window read -- up to
+// five words from the word of its first letter -- never leaves them).  A tile is the 64 window starts of one wave.
+struct ScanLayout {
+  long valid_words, letter_words;   // 64-bit words of the validity plane, 32-bit words of the letters
+  int tiles;                        // tiles of 64 window starts
+};
+inline ScanLayout scan_layout(long n, long starts) {
+  ScanLayout s;
+  s.valid_words = (n + 63) / 64 + 2;
+  s.letter_words = 4 * s.valid_words;
+  s.tiles = (int)((starts + 63) / 64);
+  return s;
+}
 // Largest motif length the letter windows hold (two 64-bit words); the number of motifs is
 // bounded by what the LDS holds (tables + one chain: choose_gibbs_geometry refuses beyond)
 // and by the statistics kernel (one role of 64 threads per 16 motifs, at most 1024 threads per block).

@@ -147,6 +147,57 @@ def fastaToCodes(filename):
     return seqsToCodes([r.seq for r in readSeqsFromFasta(filename)])
 
 
+# stream codes (CRBM.scanSites): the letters in either case, 4 = no letter for N and the IUPAC ambiguity codes
+_STREAM_LUT = _LUT.copy()
+for _ch in "NRYSWKMBDHVU":
+    if _STREAM_LUT[ord(_ch)] == 255:
+        _STREAM_LUT[ord(_ch)] = 4
+        _STREAM_LUT[ord(_ch.lower())] = 4
+STREAM_GAP = 4
+
+
+def seqsToStream(seqs, names=None):
+    """Strings of any length -> (stream, offsets, names) for CRBM.scanSites: `stream` is one uint8 array, the records'
+    codes (0..3 = A,C,G,T in either case; 4 = no letter: N and the IUPAC ambiguity codes) with exactly one code 4
+    between two records; `offsets` (int64, len(seqs) + 1) holds the stream positions of the record starts, the last
+    entry closing the last record (record i is stream[offsets[i]:offsets[i+1] - 1]); `names` defaults to seq<i>.
+    Any other character raises.  Records may be empty."""
+    seqs = [s if isinstance(s, str) else str(getattr(s, "seq", s)) for s in seqs]
+    if names is None:
+        names = ["seq{:d}".format(i) for i in range(len(seqs))]
+    names = list(names)
+    if len(names) != len(seqs):
+        raise ValueError("names: one per record")
+    lengths = np.array([len(s) for s in seqs], dtype=np.int64)
+    offsets = np.zeros(len(seqs) + 1, dtype=np.int64)
+    np.cumsum(lengths + 1, out=offsets[1:])
+    try:
+        raw = np.frombuffer("\n".join(seqs).encode("ascii"), dtype=np.uint8)
+    except UnicodeEncodeError:
+        raise ValueError("sequences may only contain A, C, G, T, N and the IUPAC ambiguity codes")
+    lut = _STREAM_LUT.copy()
+    lut[ord("\n")] = 254                                     # the separators (a newline inside a record is refused below)
+    stream = lut[raw]
+    if stream.size:
+        sep = np.zeros(stream.size, dtype=bool)
+        sep[offsets[1:-1] - 1] = True
+        if (stream[~sep] > 4).any() or (stream[sep] != 254).any():
+            raise ValueError("sequences may only contain A, C, G, T, N and the IUPAC ambiguity codes")
+        stream[sep] = STREAM_GAP
+    return np.ascontiguousarray(stream), offsets, names
+
+
+def fastaToStream(filename):
+    """FASTA file -> (stream, offsets, names) of seqsToStream, names = the record ids.  Unlike readSeqsFromFasta the
+    reader keeps records that contain N: scanning is what they are for."""
+    ids, seqs = [], []
+    with open(filename) as f:
+        for header, seq in _iterFasta(f):
+            ids.append(header.split(None, 1)[0] if header.strip() else "")
+            seqs.append(seq)
+    return seqsToStream(seqs, ids)
+
+
 def load_sample(filename=None):
     """One-hot sample data (sequences.py:120-134).  The reference ships an Oct4
     ChIP-seq FASTA inside its package; this package carries no data files, so

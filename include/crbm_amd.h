@@ -225,6 +225,24 @@ int crbm_motif_sites_resident(crbm_handle* h, int32_t start, int32_t end, float 
                               crbm_site* sites, int64_t* count, int32_t* best_start, int32_t* best_strand,
                               float* best_prob);
 
+/* ---- stream scan: motif sites of whole records, any length, gaps allowed ---------
+ * A stream is T codes, one byte each: 0..3 = A,C,G,T, 4 = no letter here (an N, an ambiguity code, the separator
+ * between two records).  A window [s, s+M) is valid when all of its M codes are letters.  A valid window has the
+ * scores crbm_motif_sites gives the same M letters anywhere in a row (the same bits), strands reported alike: 0
+ * single-stranded, +1 / -1 double-stranded.  A site is a valid window, motif and strand with prob >= threshold; an
+ * invalid window yields nothing; a stream shorter than M, or without a valid window, yields zero records and no error.
+ * Records reuse crbm_site: seq is 0, start is the stream position of the window (hence T <= 2^31 - 1).  They come
+ * sorted by (start, motif, strand), + before -: position order.  At most `capacity` of them are written to `sites`;
+ * `*count` is always the exact total.  sites == NULL with capacity 0 only counts.  The same bits in every run and for
+ * every CRBM_SLAB_BYTES (the stream goes through the device in segments of window starts, each with a halo of M - 1
+ * letters, one byte per letter).
+ * Served: DNA models without pooling on the specialised kernels, and those that run as slabs of motifs on them.
+ * CRBM_ERR_INVALID: threshold outside [0,1], a code above 4, a negative T or capacity, T > 2^31 - 1; pooling > 1
+ * (pool groups have no anchor in a stream), an alphabet other than DNA's, a model that runs on the generic kernels
+ * alone (motifs beyond 64 letters).  The handle stays usable after a refusal. */
+int crbm_scan_sites_codes(crbm_handle* h, const uint8_t* codes, int64_t T, float threshold, int64_t capacity,
+                          crbm_site* sites, int64_t* count);
+
 /* ---- in-silico mutagenesis and pseudo-log-likelihood -----------------------------
  * WHICH bases matter.  With F(v) = L * crbm_free_energy(v), the unnormalised free energy of one sequence (derived from
  * theano_freeEnergyForData, convRBM.py:657-676: the hidden terms of all motifs and strands, pooled form when

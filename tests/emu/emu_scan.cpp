@@ -1,0 +1,128 @@
+// TEST INFRASTRUCTURE: runs the stream-scan kernels of crbm_amd/csrc/crbm_kernels.h (scan_encode_kernel, scan_sites_body
+// in both passes, scan_offsets_kernel) on CPU threads under ASan/UBSan, like emu_sites.cpp does for the motif-site
+// kernels.  Every buffer has exactly the size of scan_layout (crbm_layout.h), so that ASan sees any overrun.  Plain C
+// entry points for tests/test_emu_scan.py (ctypes).
+#define CRBM_DEFINE_MISC_KERNELS
+#include "crbm_kernels.h"
+
+#include <cstring>
+#include <thread>
+#include <vector>
+
+// declared by crbm_kernels.h for the motif-site kernels of the same header; the scan does not use it
+unsigned long long atomicMax(unsigned long long* p, unsigned long long v) {
+  unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (old < v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return old;
+}
+
+namespace emu {
+thread_local dim3 t_threadIdx, t_blockIdx, t_blockDim, t_gridDim;
+thread_local BlockCtx* t_ctx;
+
+// all blocks of the grid at once, as concurrent OS threads
+template <typename F>
+void launch(F kernel, dim3 grid, dim3 block, size_t lds) {
+  const unsigned nthr = block.x, nwaves = (block.x + 63) / 64, nblocks = grid.x * grid.y;
+  std::vector<BlockCtx> ctx(nblocks);
+  std::vector<std::vector<pthread_barrier_t>> wb(nblocks, std::vector<pthread_barrier_t>(nwaves));
+  std::vector<std::vector<float>> scratch(nblocks, std::vector<float>(nwaves * 64));
+  std::vector<std::vector<uint32_t>> frag(nblocks, std::vector<uint32_t>((size_t)nwaves * 64 * 8));
+  std::vector<std::vector<float4>> smem(nblocks, std::vector<float4>((lds + 15) / 16 + 1));   // exact size: ASan sees overruns
+  std::vector<std::thread> threads;
+  threads.reserve((size_t)nblocks * nthr);
+  for (unsigned b = 0; b < nblocks; ++b) {
+    pthread_barrier_init(&ctx[b].bar, nullptr, nthr);
+    for (unsigned w = 0; w < nwaves; ++w) pthread_barrier_init(&wb[b][w], nullptr, std::min(64u, nthr - w * 64));
+    memset(smem[b].data(), 0xAB, smem[b].size() * 16);
+    ctx[b].wave_bar = wb[b].data();
+    ctx[b].wave_scratch = scratch[b].data();
+    ctx[b].wave_frag = frag[b].data();
+    ctx[b].smem = reinterpret_cast<unsigned char*>(smem[b].data());
+    for (unsigned t = 0; t < nthr; ++t)
+      threads.emplace_back([&, b, t]() {
+        t_threadIdx = dim3(t, 0, 0);
+        t_blockIdx = dim3(b % grid.x, b / grid.x, 0);
+        t_blockDim = block;
+        t_gridDim = grid;
+        t_ctx = &ctx[b];
+        kernel();
+      });
+  }
+  for (auto& th : threads) th.join();
+  for (unsigned b = 0; b < nblocks; ++b) {
+    pthread_barrier_destroy(&ctx[b].bar);
+    for (auto& w : wb[b]) pthread_barrier_destroy(&w);
+  }
+}
+}  // namespace emu
+
+using namespace crbm;
+
+// the model configurations of the scan cases (K, M, DS, G)
+#define SCAN_DISPATCH(id, ...)                                           \
+  switch (id) {                                                          \
+    case 0: { using C = Cfg<10, 15, 1, 3>; __VA_ARGS__; break; }         \
+    case 1: { using C = Cfg<10, 5, 0, 2>; __VA_ARGS__; break; }          \
+    case 2: { using C = Cfg<6, 1, 1, 1>; __VA_ARGS__; break; }           \
+    case 3: { using C = Cfg<20, 15, 1, 2>; __VA_ARGS__; break; }         /* two groups of quads */ \
+    case 4: { using C = Cfg<36, 6, 0, 2>; __VA_ARGS__; break; }          /* three */ \
+    case 5: { using C = Cfg<5, 40, 1, 2>; __VA_ARGS__; break; }          /* a window of two 64-bit words */ \
+    default: return -1;                                                  \
+  }
+
+extern "C" {
+
+int emu_scan_info(int id, int* out) {   // K, M, DS, TABLES
+  SCAN_DISPATCH(id, (out[0] = C::K, out[1] = C::M, out[2] = C::DS, out[3] = C::TABLES_ALL));
+  return 0;
+}
+
+int emu_scan_tables(int id, const float* W, const float* b, const float* c, float* out) {
+  TablesArgs a{W, b, c, out};
+  SCAN_DISPATCH(id, emu::launch([&] { build_tables_body<C>(a); }, dim3(2), dim3(64), 0));
+  return 0;
+}
+
+// The whole scan of a stream of T codes as one segment: encode, count, offsets, write.  recs holds `capacity` records
+// (plus whatever guard the caller keeps behind them); *count gets the exact total, *flags the encode kernel's flag.
+// valid_out / letters_out (optional) receive the planes of scan_layout.  Returns the number of tiles, -2 for T < M.
+int emu_scan_run(int id, const float* tables, const unsigned char* codes, long T, float threshold, SiteRec* recs,
+                 unsigned long long capacity, unsigned long long* count, uint32_t* flags, int grid, int threads,
+                 unsigned long long* valid_out, uint32_t* letters_out) {
+  int M = 0, tab = 0;
+  SCAN_DISPATCH(id, (M = C::M, tab = C::TAB));
+  if (T < M) return -2;
+  const long starts = T - M + 1;
+  const ScanLayout l = scan_layout(T, starts);
+  std::vector<uint32_t> staged((size_t)(T + 3) / 4);                    // 4-byte aligned, as the driver's staging buffer
+  std::memcpy(staged.data(), codes, (size_t)T);
+  std::vector<uint32_t> letters((size_t)l.letter_words, 0xDEADBEEFu);
+  std::vector<unsigned long long> valid((size_t)l.valid_words, ~0ull);
+  std::vector<unsigned short> lanes((size_t)64 * l.tiles, 0xFFFFu);
+  std::vector<uint32_t> tiles((size_t)l.tiles, 0xFFFFFFFFu);
+  std::vector<unsigned long long> off((size_t)l.tiles + 1, ~0ull);
+  ScanEncodeArgs e{reinterpret_cast<const unsigned char*>(staged.data()), letters.data(), valid.data(), flags, T, l.valid_words};
+  // the encode kernel reads whole 32-bit words only where four codes exist: hand it the exact byte count
+  emu::launch([&] { scan_encode_kernel(e); }, dim3(2), dim3(64), 0);
+  if (valid_out) std::memcpy(valid_out, valid.data(), valid.size() * 8);
+  if (letters_out) std::memcpy(letters_out, letters.data(), letters.size() * 4);
+  ScanArgs a;
+  a.tables = tables; a.letters = letters.data(); a.valid = valid.data();
+  a.lane_cnt = lanes.data(); a.tile_cnt = tiles.data(); a.tile_off = off.data();
+  a.recs = recs; a.capacity = capacity;
+  a.starts = (int)starts; a.tiles = l.tiles; a.pos0 = 0; a.pass = 0; a.threshold = threshold;
+  a.table_stride = 0;
+  SCAN_DISPATCH(id, (a.plan.Ks = C::K, a.plan.K = C::K, a.plan.last_k0 = 0,
+                     emu::launch([&] { scan_sites_body<C>(a); }, dim3(grid), dim3(threads), (size_t)tab * 4)));
+  ScanOffsetsArgs o{tiles.data(), off.data(), off.data() + l.tiles, l.tiles};
+  emu::launch([&] { scan_offsets_kernel(o); }, dim3(1), dim3(128), 128 * 8);
+  *count = off[(size_t)l.tiles];
+  if (recs) {
+    a.pass = 1;
+    SCAN_DISPATCH(id, emu::launch([&] { scan_sites_body<C>(a); }, dim3(grid), dim3(threads), (size_t)tab * 4));
+  }
+  return l.tiles;
+}
+
+}  // extern "C"
