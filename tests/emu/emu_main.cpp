@@ -4,49 +4,10 @@
 // a GPU.  Exposes plain C entry points for tests/emu/run_emu.py (ctypes).
 #define CRBM_DEFINE_MISC_KERNELS
 #include "crbm_kernels.h"
+#include "emu_launch.h"
 
-#include <thread>
-#include <vector>
-
-namespace emu {
-thread_local dim3 t_threadIdx, t_blockIdx, t_blockDim, t_gridDim;
-thread_local BlockCtx* t_ctx;
-
-template <typename F>
-void launch(F kernel, dim3 grid, dim3 block, size_t lds) {
-  const unsigned nthr = block.x, nwaves = (block.x + 63) / 64;
-  for (unsigned by = 0; by < grid.y; ++by)
-    for (unsigned bx = 0; bx < grid.x; ++bx) {
-      BlockCtx ctx;
-      pthread_barrier_init(&ctx.bar, nullptr, nthr);
-      std::vector<pthread_barrier_t> wb(nwaves);
-      for (unsigned w = 0; w < nwaves; ++w) pthread_barrier_init(&wb[w], nullptr, std::min(64u, nthr - w * 64));
-      std::vector<float> scratch(nwaves * 64);
-      std::vector<uint32_t> frag((size_t)nwaves * 64 * 8);
-      // exact size (16-byte aligned base): out-of-bounds LDS accesses trip AddressSanitizer
-      std::vector<float4> smem((lds + 15) / 16 + 1);
-      memset(smem.data(), 0xAB, smem.size() * 16);
-      ctx.wave_bar = wb.data();
-      ctx.wave_scratch = scratch.data();
-      ctx.wave_frag = frag.data();
-      ctx.smem = reinterpret_cast<unsigned char*>(smem.data());
-      std::vector<std::thread> threads;
-      threads.reserve(nthr);
-      for (unsigned t = 0; t < nthr; ++t)
-        threads.emplace_back([&, t]() {
-          t_threadIdx = dim3(t, 0, 0);
-          t_blockIdx = dim3(bx, by, 0);
-          t_blockDim = block;
-          t_gridDim = grid;
-          t_ctx = &ctx;
-          kernel();
-        });
-      for (auto& th : threads) th.join();
-      pthread_barrier_destroy(&ctx.bar);
-      for (auto& b : wb) pthread_barrier_destroy(&b);
-    }
-}
-}  // namespace emu
+// block after block: run_emu.py compares some results bit for bit, and its grids are large
+const bool emu::concurrent_blocks = false;
 
 using namespace crbm;
 
@@ -90,8 +51,7 @@ int emu_case_info(int id, int* out) {   // K, M, DS, G, TABLES, NW, DENSE, POOL
 }
 
 int emu_encode(const float* v, uint32_t* letters, uint32_t* flags, int n, int L, int grid) {
-  EncodeArgs a{v, letters, flags, n, L, letter_words(L), 4};
-  emu::launch([&] { encode_onehot_kernel(a); }, dim3(grid), dim3(64), 0);
+  emu::encode_onehot(v, letters, flags, n, L, grid);
   return 0;
 }
 
@@ -144,8 +104,7 @@ int emu_pack_hidden(float* dense, uint32_t* masks, uint32_t* flags, int n, int K
 }
 
 int emu_tables(int id, const float* W, const float* b, const float* c, float* out) {
-  TablesArgs a{W, b, c, out};
-  CFG_DISPATCH(id, emu::launch([&] { build_tables_body<C>(a); }, dim3(3), dim3(64), 0));
+  CFG_DISPATCH(id, emu::build_tables<C>(W, b, c, out, 3));
   return 0;
 }
 

@@ -4,58 +4,12 @@
 // entry points for tests/test_emu_scan.py (ctypes).
 #define CRBM_DEFINE_MISC_KERNELS
 #include "crbm_kernels.h"
+#include "emu_launch.h"
 
 #include <cstring>
-#include <thread>
-#include <vector>
-
-// declared by crbm_kernels.h for the motif-site kernels of the same header; the scan does not use it
-unsigned long long atomicMax(unsigned long long* p, unsigned long long v) {
-  unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
-  while (old < v && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-  return old;
-}
-
-namespace emu {
-thread_local dim3 t_threadIdx, t_blockIdx, t_blockDim, t_gridDim;
-thread_local BlockCtx* t_ctx;
 
 // all blocks of the grid at once, as concurrent OS threads
-template <typename F>
-void launch(F kernel, dim3 grid, dim3 block, size_t lds) {
-  const unsigned nthr = block.x, nwaves = (block.x + 63) / 64, nblocks = grid.x * grid.y;
-  std::vector<BlockCtx> ctx(nblocks);
-  std::vector<std::vector<pthread_barrier_t>> wb(nblocks, std::vector<pthread_barrier_t>(nwaves));
-  std::vector<std::vector<float>> scratch(nblocks, std::vector<float>(nwaves * 64));
-  std::vector<std::vector<uint32_t>> frag(nblocks, std::vector<uint32_t>((size_t)nwaves * 64 * 8));
-  std::vector<std::vector<float4>> smem(nblocks, std::vector<float4>((lds + 15) / 16 + 1));   // exact size: ASan sees overruns
-  std::vector<std::thread> threads;
-  threads.reserve((size_t)nblocks * nthr);
-  for (unsigned b = 0; b < nblocks; ++b) {
-    pthread_barrier_init(&ctx[b].bar, nullptr, nthr);
-    for (unsigned w = 0; w < nwaves; ++w) pthread_barrier_init(&wb[b][w], nullptr, std::min(64u, nthr - w * 64));
-    memset(smem[b].data(), 0xAB, smem[b].size() * 16);
-    ctx[b].wave_bar = wb[b].data();
-    ctx[b].wave_scratch = scratch[b].data();
-    ctx[b].wave_frag = frag[b].data();
-    ctx[b].smem = reinterpret_cast<unsigned char*>(smem[b].data());
-    for (unsigned t = 0; t < nthr; ++t)
-      threads.emplace_back([&, b, t]() {
-        t_threadIdx = dim3(t, 0, 0);
-        t_blockIdx = dim3(b % grid.x, b / grid.x, 0);
-        t_blockDim = block;
-        t_gridDim = grid;
-        t_ctx = &ctx[b];
-        kernel();
-      });
-  }
-  for (auto& th : threads) th.join();
-  for (unsigned b = 0; b < nblocks; ++b) {
-    pthread_barrier_destroy(&ctx[b].bar);
-    for (auto& w : wb[b]) pthread_barrier_destroy(&w);
-  }
-}
-}  // namespace emu
+const bool emu::concurrent_blocks = true;
 
 using namespace crbm;
 
@@ -79,8 +33,7 @@ int emu_scan_info(int id, int* out) {   // K, M, DS, TABLES
 }
 
 int emu_scan_tables(int id, const float* W, const float* b, const float* c, float* out) {
-  TablesArgs a{W, b, c, out};
-  SCAN_DISPATCH(id, emu::launch([&] { build_tables_body<C>(a); }, dim3(2), dim3(64), 0));
+  SCAN_DISPATCH(id, emu::build_tables<C>(W, b, c, out));
   return 0;
 }
 

@@ -12,39 +12,25 @@ Runs set aside as tied on the development machine: 0 of 6 in every case.
 The cases run in a subprocess with the sanitizer runtime preloaded: this file is also that subprocess's script."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMU = os.path.join(HERE, "emu")
-CSRC = os.path.join(ROOT, "crbm_amd", "csrc")
-LIB = os.path.join(EMU, "libcrbm_emu_ais.so")
-SOURCES = [os.path.join(EMU, "emu_ais.cpp"), os.path.join(EMU, "shim", "hip", "hip_runtime.h"),
-           os.path.join(CSRC, "crbm_kernels.h"), os.path.join(CSRC, "crbm_layout.h")]
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # also when run as the child's script
+from tests.emu import harness  # noqa: E402
+from tests.emu.harness import fp  # noqa: E402
+
+LIB = "libcrbm_emu_ais.so"
 RTOL = 2e-5          # the emulation's tolerance (tests/test_emu_sites.py)
 GUARD = 16
 T, RUNS, SEED = 8, 6, 77
 
 
-def _gcc_file(name):
-    return subprocess.check_output(["gcc", "-print-file-name=" + name], text=True).strip()
-
-
 @pytest.fixture(scope="module")
 def emu_env():
-    if not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in SOURCES):
-        cmd = ["g++", "-std=c++17", "-O1", "-g1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-               "-fno-sanitize-recover=undefined", "-mf16c", "-fPIC", "-shared", "-I", os.path.join(EMU, "shim"), "-I", CSRC,
-               os.path.join(EMU, "emu_ais.cpp"), "-o", LIB, "-lpthread"]
-        subprocess.check_call(cmd)
-    env = dict(os.environ)
-    env["LD_PRELOAD"] = _gcc_file("libasan.so") + ":" + _gcc_file("libubsan.so")
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=1"
-    return env
+    harness.build("emu_ais.cpp", LIB)
+    return harness.child_env()
 
 
 # name -> (configuration of emu_ais.cpp, L, base-rate bias of its own?)
@@ -54,42 +40,22 @@ CASES = {"ds_10x15": (0, 75, True), "ss_10x5": (1, 83, False), "m1": (2, 37, Tru
 
 @pytest.mark.parametrize("which", list(CASES))
 def test_ais_kernel_on_cpu_threads_with_sanitizers(emu_env, which):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), which], env=emu_env, capture_output=True, text=True,
-                       timeout=1800)
+    r = harness.run_case(os.path.abspath(__file__), which, emu_env, timeout=1800)
     assert r.returncode == 0 and "AIS OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
     print(r.stdout[-600:])
 
 
 # ---- the subprocess side -------------------------------------------------------------------------------------------
-fp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def _oracle(K, M, ds, seed):
-    from oracle.crbm_oracle import OracleCRBM
-    rng = np.random.default_rng(seed)
-    o = OracleCRBM(K, M, doublestranded=ds, batchsize=4, cd_k=1, fantasy_hidden_len=20, seed=1,
-                   W=rng.standard_normal((K, 1, 4, M)).astype(np.float32) * 0.7)
-    o.b = (o.b + 3.0 + rng.standard_normal((1, K)) * 0.5).astype(np.float32).astype(np.float64)
-    o.c = (rng.standard_normal((1, 4)) * 0.3).astype(np.float32).astype(np.float64)
-    return o
-
-
 def run_case(which):
-    sys.path.insert(0, ROOT)
     from tests import ais_reference as ref
-    lib = ctypes.CDLL(LIB)
+    lib = harness.load(LIB)
     lib.emu_ais_run.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 4 + [ctypes.c_uint32, ctypes.c_uint64,
                                                                                              ctypes.c_int, ctypes.c_int]
     cid, L, own_base = CASES[which]
-    info = (ctypes.c_int * 4)()
-    lib.emu_ais_info(cid, info)
-    K, M, DS, TABLES = list(info)
-    o = _oracle(K, M, bool(DS), seed=K + M)
-    W = np.ascontiguousarray(o.W.reshape(K, 4, M), dtype=np.float32)
-    b = np.ascontiguousarray(o.b.ravel(), dtype=np.float32)
+    K, M, DS = harness.case_info(lib.emu_ais_info, cid)[:3]
+    o = harness.random_model(K, M, bool(DS), K + M, draw_c=True)
+    tables = harness.model_tables(lib.emu_ais_info, lib.emu_ais_tables, cid, o, tables_at=3)
     c = np.ascontiguousarray(o.c.ravel(), dtype=np.float32)
-    tables = np.zeros(TABLES, np.float32)
-    lib.emu_ais_tables(cid, fp(W), fp(b), fp(c), fp(tables))
     cA = np.log(np.array([0.3, 0.2, 0.15, 0.35])).astype(np.float32) if own_base else c
     betas = np.linspace(0.0, 1.0, T + 1).astype(np.float32)
 

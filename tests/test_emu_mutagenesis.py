@@ -7,41 +7,26 @@ free-energy pass and combine for a pooled and a double-stranded model, and expan
 Guard words around every output stay untouched.
 
 The cases run in a subprocess with the sanitizer runtime preloaded: this file is also that subprocess's script."""
-import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMU = os.path.join(HERE, "emu")
-CSRC = os.path.join(ROOT, "crbm_amd", "csrc")
-LIB = os.path.join(EMU, "libcrbm_emu_mutagenesis.so")
-SOURCES = [os.path.join(EMU, "emu_mutagenesis.cpp"), os.path.join(EMU, "shim", "hip", "hip_runtime.h"),
-           os.path.join(CSRC, "crbm_kernels.h"), os.path.join(CSRC, "crbm_kernels_generic.h"), os.path.join(CSRC, "crbm_layout.h")]
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # also when run as the child's script
+from tests.emu import harness  # noqa: E402
+from tests.emu.harness import fp  # noqa: E402
+
+LIB = "libcrbm_emu_mutagenesis.so"
 RTOL = 2e-5          # the emulation's tolerance (tests/test_emu_sites.py), applied at the scale of the output
 GUARD = 8
 SENTINEL = np.float32(-12345.5)
 
 
-def _gcc_file(name):
-    return subprocess.check_output(["gcc", "-print-file-name=" + name], text=True).strip()
-
-
 @pytest.fixture(scope="module")
 def emu_env():
-    if not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in SOURCES):
-        cmd = ["g++", "-std=c++17", "-O1", "-g1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-               "-fno-sanitize-recover=undefined", "-mf16c", "-fPIC", "-shared", "-I", os.path.join(EMU, "shim"), "-I", CSRC,
-               os.path.join(EMU, "emu_mutagenesis.cpp"), "-o", LIB, "-lpthread"]
-        subprocess.check_call(cmd)
-    env = dict(os.environ)
-    env["LD_PRELOAD"] = _gcc_file("libasan.so") + ":" + _gcc_file("libubsan.so")
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=1"
-    return env
+    harness.build("emu_mutagenesis.cpp", LIB)
+    return harness.child_env()
 
 
 CASES = ["ds_10x15", "ss_10x5", "m1", "one_window", "three_chunks", "m40", "general_pool2", "general_ds", "general_alpha5"]
@@ -49,24 +34,11 @@ CASES = ["ds_10x15", "ss_10x5", "m1", "one_window", "three_chunks", "m40", "gene
 
 @pytest.mark.parametrize("which", CASES)
 def test_mutagenesis_kernels_on_cpu_threads_with_sanitizers(emu_env, which):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), which], env=emu_env, capture_output=True, text=True,
-                       timeout=900)
+    r = harness.run_case(os.path.abspath(__file__), which, emu_env, timeout=900)
     assert r.returncode == 0 and "MUTAGENESIS OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 # ---- the subprocess side -------------------------------------------------------------------------------------------
-def _oracle(K, M, ds, pool, seed, A=4):
-    sys.path.insert(0, ROOT)
-    from oracle.crbm_oracle import OracleCRBM
-    rng = np.random.default_rng(seed)
-    kw = {"input_dims": A} if A != 4 else {}
-    o = OracleCRBM(K, M, doublestranded=ds, batchsize=4, cd_k=1, fantasy_hidden_len=20, seed=1, pooling=pool,
-                   W=rng.standard_normal((K, 1, A, M)).astype(np.float32) * 0.7, **kw)
-    o.b = (o.b + 3.0 + rng.standard_normal((1, K)) * 0.5).astype(np.float32).astype(np.float64)
-    o.c = (rng.standard_normal((1, A)) * 0.3).astype(np.float32).astype(np.float64)
-    return o
-
-
 def _onehot(codes, A):
     return np.ascontiguousarray(np.eye(A, dtype=np.float32)[codes].transpose(0, 2, 1)[:, None])
 
@@ -114,24 +86,14 @@ def _guards_ok(buf):
     return np.all(buf[:GUARD] == SENTINEL) and np.all(buf[-GUARD:] == SENTINEL)
 
 
-fp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-
-
 def _setup(lib, cid, o, codes):
-    info = (ctypes.c_int * 6)()
-    lib.emu_mut_info(cid, info)
-    K, M, DS, POOL, TABLES, TAB = list(info)
     n, L = codes.shape
-    W = np.ascontiguousarray(o.W.reshape(K, 4, M), dtype=np.float32)
-    b = np.ascontiguousarray(o.b.ravel(), dtype=np.float32)
-    c = np.ascontiguousarray(o.c.ravel(), dtype=np.float32)
-    tables = np.zeros(TABLES, np.float32)
-    lib.emu_mut_tables(cid, fp(W), fp(b), fp(c), fp(tables))
+    tables = harness.model_tables(lib.emu_mut_info, lib.emu_mut_tables, cid, o, tables_at=4)
     letters = np.zeros((n, lib.emu_mut_letter_words(4, L)), np.uint32)
     flags = np.zeros(4, np.uint32)
     lib.emu_mut_encode(fp(_onehot(codes, 4)), fp(letters), fp(flags), n, L)
     assert flags[0] == 0
-    return tables, letters, c
+    return tables, letters, np.ascontiguousarray(o.c.ravel(), dtype=np.float32)
 
 
 def run_fused(lib, cid, tables, letters, n, L, want_dfe=True, want_pll=True, grid=2, threads=128):
@@ -185,12 +147,11 @@ def expected_copies(codes, A):
 
 
 def run_case(which):
-    sys.path.insert(0, ROOT)
-    lib = ctypes.CDLL(LIB)
+    lib = harness.load(LIB)
     if which == "general_alpha5":
         # bytes per letter: the expand kernel against NumPy, the combine kernel on the oracle's per-motif free energies
         A, K, M, n, L = 5, 7, 6, 3, 23
-        o = _oracle(K, M, False, 1, seed=5, A=A)
+        o = harness.random_model(K, M, False, 5, A=A, draw_c=True)
         codes = np.random.default_rng(8).integers(0, A, size=(n, L), dtype=np.uint8)
         LW = lib.emu_mut_letter_words(A, L)
         letters = np.zeros((n, LW), np.uint32)
@@ -214,10 +175,8 @@ def run_case(which):
         return
     cid, n, L = {"ds_10x15": (0, 5, 75), "ss_10x5": (1, 5, 83), "m1": (2, 4, 37), "one_window": (0, 3, 15),
                  "three_chunks": (3, 3, 150), "m40": (4, 3, 90), "general_pool2": (5, 3, 48), "general_ds": (0, 3, 45)}[which]
-    info = (ctypes.c_int * 6)()
-    lib.emu_mut_info(cid, info)
-    K, M, DS, POOL, _, _ = list(info)
-    o = _oracle(K, M, bool(DS), POOL, seed=K + M)
+    K, M, DS, POOL = harness.case_info(lib.emu_mut_info, cid)[:4]
+    o = harness.random_model(K, M, bool(DS), K + M, pool=POOL, draw_c=True)
     codes = np.random.default_rng(K * 3 + L).integers(0, 4, size=(n, L), dtype=np.uint8)
     tables, letters, c = _setup(lib, cid, o, codes)
     want, wpll = oracle_mutagenesis(o, codes, 4)

@@ -6,38 +6,24 @@ double-stranded, pooled and single-stranded models, and of a sequence long enoug
 The cases run in a subprocess with the sanitizer runtime preloaded: this file is also that subprocess's script."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMU = os.path.join(HERE, "emu")
-CSRC = os.path.join(ROOT, "crbm_amd", "csrc")
-LIB = os.path.join(EMU, "libcrbm_emu_sites.so")
-SOURCES = [os.path.join(EMU, "emu_sites.cpp"), os.path.join(EMU, "shim", "hip", "hip_runtime.h"),
-           os.path.join(CSRC, "crbm_kernels.h"), os.path.join(CSRC, "crbm_kernels_generic.h"), os.path.join(CSRC, "crbm_layout.h")]
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # also when run as the child's script
+from tests.emu import harness  # noqa: E402
+from tests.emu.harness import fp  # noqa: E402
+
+LIB = "libcrbm_emu_sites.so"
 RTOL = 2e-5
 REC = np.dtype([("seq", "<i4"), ("motif", "<i4"), ("start", "<i4"), ("strand", "<i4"), ("prob", "<f4")])   # SiteRec
 
 
-def _gcc_file(name):
-    return subprocess.check_output(["gcc", "-print-file-name=" + name], text=True).strip()
-
-
 @pytest.fixture(scope="module")
 def emu_env():
-    if not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in SOURCES):
-        cmd = ["g++", "-std=c++17", "-O1", "-g1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-               "-fno-sanitize-recover=undefined", "-mf16c", "-fPIC", "-shared", "-I", os.path.join(EMU, "shim"), "-I", CSRC,
-               os.path.join(EMU, "emu_sites.cpp"), "-o", LIB, "-lpthread"]
-        subprocess.check_call(cmd)
-    env = dict(os.environ)
-    env["LD_PRELOAD"] = _gcc_file("libasan.so") + ":" + _gcc_file("libubsan.so")
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=1"
-    return env
+    harness.build("emu_sites.cpp", LIB)
+    return harness.child_env()
 
 
 CASES = ["ds_10x15", "ds_6x7_pool2", "ss_10x5", "two_chunks", "tiny_capacity", "select"]
@@ -45,22 +31,11 @@ CASES = ["ds_10x15", "ds_6x7_pool2", "ss_10x5", "two_chunks", "tiny_capacity", "
 
 @pytest.mark.parametrize("which", CASES)
 def test_site_kernels_on_cpu_threads_with_sanitizers(emu_env, which):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), which], env=emu_env, capture_output=True, text=True,
-                       timeout=900)
+    r = harness.run_case(os.path.abspath(__file__), which, emu_env, timeout=900)
     assert r.returncode == 0 and "SITES OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 # ---- the subprocess side -------------------------------------------------------------------------------------------
-def _oracle(K, M, ds, pool, seed):
-    sys.path.insert(0, ROOT)
-    from oracle.crbm_oracle import OracleCRBM
-    rng = np.random.default_rng(seed)
-    o = OracleCRBM(K, M, doublestranded=ds, batchsize=4, cd_k=1, fantasy_hidden_len=20, seed=1, pooling=pool,
-                   W=rng.standard_normal((K, 1, 4, M)).astype(np.float32) * 0.7)
-    o.b = (o.b + 3.0 + rng.standard_normal((1, K)) * 0.5).astype(np.float32).astype(np.float64)
-    return o
-
-
 def oracle_scores(o, D):
     """(S, n, K, Lh) float64: the + (or single) strand, then the reverse-complemented filter"""
     if o.doublestranded:
@@ -106,16 +81,8 @@ def check_best(keys, P, ds):
 
 
 def _run_fused(lib, cid, o, D, thr, capacity, grid=2, threads=128):
-    fp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    info = (ctypes.c_int * 6)()
-    lib.emu_sites_info(cid, info)
-    K, M, DS, POOL, TABLES, HIT_NI = list(info)
-    n, L = D.shape[0], D.shape[3]
-    W = np.ascontiguousarray(o.W.reshape(K, 4, M), dtype=np.float32)
-    b = np.ascontiguousarray(o.b.ravel(), dtype=np.float32)
-    c = np.ascontiguousarray(o.c.ravel(), dtype=np.float32)
-    tables = np.zeros(TABLES, np.float32)
-    lib.emu_sites_tables(cid, fp(W), fp(b), fp(c), fp(tables))
+    n, L, K = D.shape[0], D.shape[3], o.num_motifs
+    tables = harness.model_tables(lib.emu_sites_info, lib.emu_sites_tables, cid, o, tables_at=4)
     letters = np.zeros((n, lib.emu_sites_letter_words(L)), np.uint32)
     flags = np.zeros(4, np.uint32)
     lib.emu_sites_encode(fp(np.ascontiguousarray(D, dtype=np.float32)), fp(letters), fp(flags), n, L)
@@ -131,14 +98,12 @@ def _run_fused(lib, cid, o, D, thr, capacity, grid=2, threads=128):
 
 
 def run_case(which):
-    sys.path.insert(0, ROOT)
     from oracle.crbm_oracle import synthetic_onehot
-    lib = ctypes.CDLL(LIB)
+    lib = harness.load(LIB)
     if which == "select":
         # the generic models' pass: dense oracle probabilities in, the same records and keys out (both strands, one)
-        fp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
         for ds, pool, (n, L) in ((True, 1, (5, 150)), (False, 2, (4, 71))):
-            o = _oracle(9, 6, ds, pool, seed=11)
+            o = harness.random_model(9, 6, ds, 11, pool=pool)
             D = synthetic_onehot(n, L, seed=4)
             P = oracle_scores(o, D).astype(np.float32)
             K, Lh = 9, L - 6 + 1
@@ -168,10 +133,8 @@ def run_case(which):
         return
     cid, n, L = {"ds_10x15": (0, 6, 120), "ds_6x7_pool2": (1, 6, 96), "ss_10x5": (2, 6, 104),
                  "two_chunks": (3, 2, 400), "tiny_capacity": (0, 3, 90)}[which]
-    info = (ctypes.c_int * 6)()
-    lib.emu_sites_info(cid, info)
-    K, M, DS, POOL, _, HIT_NI = list(info)
-    o = _oracle(K, M, bool(DS), POOL, seed=K + M)
+    K, M, DS, POOL = harness.case_info(lib.emu_sites_info, cid)[:4]
+    o = harness.random_model(K, M, bool(DS), K + M, pool=POOL)
     D = synthetic_onehot(n, L, seed=K * 3 + 1)
     P = oracle_scores(o, D)
     if which == "tiny_capacity":

@@ -8,37 +8,23 @@ enqueued, drain is called once, the error is returned.
 The cases run in a subprocess with the sanitizer runtime preloaded: this file is also that subprocess's script."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-EMU = os.path.join(HERE, "emu")
-CSRC = os.path.join(ROOT, "crbm_amd", "csrc")
-LIB = os.path.join(EMU, "libcrbm_sweep_driver.so")
-SOURCES = [os.path.join(EMU, "sweep_driver.cpp"), os.path.join(CSRC, "crbm_sweep.h")]
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # also when run as the child's script
+from tests.emu import harness  # noqa: E402
+
+LIB = "libcrbm_sweep_driver.so"
 ENQUEUE, COLLECT, DRAIN = 0, 1, 2
 # (n, slab): slab >= n (one slab), slab == 1, n a multiple of slab (two, three, many slabs) and not
 SHAPES = [(1, 1), (5, 5), (5, 9), (7, 1), (2, 1), (8, 4), (9, 3), (12, 2), (9, 4), (10, 3), (11, 5), (100, 7), (3, 2)]
 
 
-def _gcc_file(name):
-    return subprocess.check_output(["gcc", "-print-file-name=" + name], text=True).strip()
-
-
 @pytest.fixture(scope="module")
 def emu_env():
-    if not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in SOURCES):
-        cmd = ["g++", "-std=c++17", "-O1", "-g1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-               "-fno-sanitize-recover=undefined", "-fPIC", "-shared", "-I", CSRC, os.path.join(EMU, "sweep_driver.cpp"),
-               "-o", LIB]
-        subprocess.check_call(cmd)
-    env = dict(os.environ)
-    env["LD_PRELOAD"] = _gcc_file("libasan.so") + ":" + _gcc_file("libubsan.so")
-    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=1"
-    return env
+    harness.build("sweep_driver.cpp", LIB, kernels=False)
+    return harness.child_env()
 
 
 CASES = ["order_depth2", "order_depth1", "errors_depth2", "errors_depth1"]
@@ -46,8 +32,7 @@ CASES = ["order_depth2", "order_depth1", "errors_depth2", "errors_depth1"]
 
 @pytest.mark.parametrize("which", CASES)
 def test_slab_driver_order_of_calls(emu_env, which):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), which], env=emu_env, capture_output=True, text=True,
-                       timeout=300)
+    r = harness.run_case(os.path.abspath(__file__), which, emu_env, timeout=300)
     assert r.returncode == 0 and "SWEEP OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
@@ -114,5 +99,5 @@ def run_case(lib, which):
 
 
 if __name__ == "__main__":
-    run_case(ctypes.CDLL(LIB), sys.argv[1])
+    run_case(harness.load(LIB), sys.argv[1])
     print("SWEEP OK")
