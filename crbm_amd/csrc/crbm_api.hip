@@ -4,6 +4,7 @@
 #define CRBM_DEFINE_MISC_KERNELS
 #include "crbm_kernels.h"
 #include "crbm_jit.h"
+#include "crbm_plan.h"
 #include "crbm_sweep.h"
 #include "../../include/crbm_amd.h"
 
@@ -73,24 +74,6 @@ bool load_rccl() {
   return true;
 }
 
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && *v) ? atoi(v) : dflt;
-}
-
-// Letter grouping of PLAIN chain launches (crbm_gibbs_steps*: one 1024-thread block per CU whose LDS is otherwise idle):
-// the largest grouping whose table stays within 48 KB -- config #2: G = 4 (49 152 B, four gathers per position) where the
-// fused training launch, four blocks per CU beside the statistics slices, takes G = 3 (five gathers): 21.7 -> 21.4 us per
-// launch.  Only for models whose training step never launches the plain kernel (Cfg::FUSE_STATS) -- the others would
-// rebuild the second table every step -- and not beyond 48 KB: every block copies its table once per launch (config #5
-// with G = 4, 82 KB: 144.6 -> 150 us).  CRBM_GROUP_SOLO overrides.
-int solo_group(int K, int M, int ds, int G, int pool) {
-  const int forced = env_int("CRBM_GROUP_SOLO", 0);
-  if (forced >= 1 && forced <= 4) return forced;
-  if (!model_shape(K, M, ds, G, pool).FUSE_STATS) return G;
-  return std::max(G, choose_group(K, M, ds, 48 * 1024));
-}
-
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
@@ -114,7 +97,16 @@ struct DevBuf {
 
 }  // namespace
 
-// One host thread per extra partition of the plain chain launches (crbm_handle::chain_parts): it enqueues that
+// The slab model of a generic DNA model (LaunchPlan::slab_K): its shape, its specialised kernels, the partial rows of its
+// statistics and, per set of a two-stream sweep, the per-motif scratch of its free energies.
+struct SlabModel {
+  int K = 0;
+  crbm::ModelShape ms = {};
+  crbm::JitKernels jk;
+  DevBuf<float> partials, partials2, fe_scratch[2];
+};
+
+// One host thread per extra partition of the plain chain launches (LaunchPlan::chain_parts): it enqueues that
 // partition's launches on the partition's stream while the caller's thread enqueues partition 0's.  Alternating two
 // streams from ONE thread costs ~6 us of host time per launch (2.6 us when a thread stays on one stream), which at two
 // launches per 17.6-us step leaves the GPU waiting for the host in short bursts.
@@ -137,7 +129,7 @@ struct PartWorker {
 
 struct crbm_handle {
   crbm_config cfg;
-  int K = 0, M = 0, ds = 0, NW = 0, G = 0, KAM = 0;
+  int K = 0, M = 0, ds = 0, NW = 0, KAM = 0;
   int A = 4;                // letters of the alphabet (input_dims); anything but 4 runs on the generic kernels, rows of bytes
   int Lf = 0, Lv = 0, B = 0;
   int device = 0, num_cu = 256;
@@ -145,13 +137,14 @@ struct crbm_handle {
   hipStream_t stream2 = nullptr;          // model phase of a training step runs beside the data phase
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
   bool overlap = false;
-  bool big = false;         // model beyond the LDS-resident kernels: the generic "big" kernels (crbm_kernels.h) serve every entry point
-  ModelShape ms;
-  ModelShape ms_solo;       // the same model with the letter grouping of plain chain launches (GS; == ms when GS == G)
-  int GS = 0;
+  // which kernels the model takes, the geometry of its chain launches, what its kernels are compiled with (crbm_plan.h:
+  // the plan crbm_precompile compiled for); launches name the ChainGeom they mean, nothing here changes after crbm_create
+  LaunchPlan plan;
+  bool big() const { return plan.big; }              // the generic "big" kernels (crbm_kernels.h) serve every entry point
+  const ModelShape& ms() const { return plan.ms; }
   JitKernels jk;            // kernels specialised for this model (hiprtc)
   float* d_tables = nullptr;   // precomputed LDS images (gather / top-down tables, c)
-  float* d_tf_solo = nullptr;  // gather table in the solo grouping (GS != G only), rebuilt lazily before a plain chain launch
+  float* d_tf_solo = nullptr;  // gather table in the solo grouping (plan.GS != plan.G only), rebuilt lazily before a plain chain launch
   bool tables_dirty = true;
   uint64_t params_version = 1, tf_solo_version = 0;   // bumped with every change of W, b, c / version d_tf_solo was built from
   // parameters and optimiser state
@@ -191,20 +184,8 @@ struct crbm_handle {
   // sampler
   uint64_t seed = 0;
   uint32_t gibbs_step = 0, eval_step = 0, chain_offset = 0;
-  // launch geometry
-  GibbsLayout gl;                      // of the variant in use
-  int gibbs_threads = 256, gibbs_grid = 0;
-  // top-down variants of the Gibbs kernel: [0] dense tables (small models only), [1] set-bit walk
-  GibbsLayout glv[2];
-  GibbsLayout gl_solo;                 // geometry of plain chain launches of the sparse variant when it differs (solo_threads > 0)
-  int solo_threads = 0, solo_grid = 0;
-  // Plain chain launches of short kernels go out as `chain_parts` launches of `part_chains` chains each, one stream per
-  // partition: chains are independent, so partition p's step t+1 only waits for partition p's step t, and the drain of
-  // one partition's kernel, the dispatch and the ramp of its next one are filled by the other partition's blocks on the
-  // same CUs (config #2: 20.9 -> 17.6 us per step of the whole batch).
-  int chain_parts = 1, part_chains = 0;
-  GibbsLayout gl_part;                 // geometry of ONE partition's launch (chain_parts > 1); solo_* / gl_solo stay the unpartitioned one,
-  int part_threads = 0, part_grid = 0; // which the chain launch INSIDE a training step takes (one launch, then the statistics wait for it)
+  int LWs = 0;                         // words per row of the last visible sample (d_vf)
+  // the streams, threads and events of the partitions of plain chain launches (plan.chain_parts > 1)
   hipStream_t part_stream[4] = {nullptr, nullptr, nullptr, nullptr};
   PartWorker* part_worker[4] = {nullptr, nullptr, nullptr, nullptr};   // [0] stays null: the caller's thread
   hipEvent_t part_done[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -219,10 +200,7 @@ struct crbm_handle {
   hipEvent_t ev_cal0 = nullptr, ev_cal1 = nullptr;
   bool cal_pending = false;
   int wall_khz = 100000;               // ticks of the GPU's wall clock per millisecond
-  int threadsv[2] = {256, 256}, gridv[2] = {0, 0};
-  bool has_dense = false;
-  int gibbs_wpe = 0;                   // register-allocation hint compiled into the sparse Gibbs kernel
-  int variant = 1;
+  int variant = 1;                     // top-down variant of the Gibbs kernel in use (plan.chain[variant]; fixed per handle)
   int topdown_mode = 0;                // CRBM_TOPDOWN: 1 dense, anything else the set-bit walk (fixed per handle)
   uint32_t* d_nset = nullptr;          // per wave of the last Gibbs launch: set bits of the final state
   int nset_slots = 0;
@@ -249,10 +227,10 @@ struct crbm_handle {
   unsigned long long* d_timeline = nullptr;   // CRBM_GIBBS_TIMELINE: first / last tick of block 0 of every launch of a crbm_time_gibbs call
   int timeline_cap = 0, timeline_next = 0;
   unsigned long long ipc_timeout_ticks = 0;   // bound of an update launch's wait for its peers, in ticks of the GPU's wall clock
-  // Statistics of a generic DNA model on the matrix cores, a slab of motifs at a time (slab_launch_stats): a shadow handle
-  // of the slab model -- slab->K motifs, its specialised kernels, its partial rows and nothing else (the stream is this
-  // handle's) -- and one table image per slab, rebuilt when the parameters have changed
-  crbm_handle* slab = nullptr;
+  // Statistics, h|v, free energies and site scans of a generic DNA model on the specialised kernels, a slab of motifs
+  // at a time: the slab model (slab.K motifs; 0: none, slab_note says why) and one table image per slab, rebuilt when
+  // the parameters have changed
+  SlabModel slab;
   float* d_slab_tables = nullptr;
   int slab_n = 0;
   bool slab_hgv = false;               // the chain's h|v takes the slabs too (slab a multiple of ten motifs, or one slab: sampler groups)
@@ -289,17 +267,17 @@ RngView rng_view(const crbm_handle* h, uint32_t step, uint32_t seq_offset) {
   return r;
 }
 
-int tab_bytes(const crbm_handle* h) { return h->ms.TAB * 4; }
+int tab_bytes(const ModelShape& ms) { return ms.TAB * 4; }
 
 // words per packed row of L letters (2-bit letters for DNA, bytes for any other alphabet)
 int lw(const crbm_handle* h, int L) { return letter_words_any(h->A, L); }
 
 // (re)build the LDS table images after a parameter change
 int ensure_tables(crbm_handle* h) {
-  if (!h->tables_dirty || h->big) return CRBM_OK;
+  if (!h->tables_dirty || h->big()) return CRBM_OK;
   TablesArgs t;
   t.W = h->dW; t.b = h->db; t.c = h->dc; t.out = h->d_tables;
-  const unsigned grid = (unsigned)std::max(1, std::min((h->ms.TABLES_ALL + 255) / 256, h->num_cu * 4));
+  const unsigned grid = (unsigned)std::max(1, std::min((h->ms().TABLES_ALL + 255) / 256, h->num_cu * 4));
   HIPCHK(jit_launch(h->jk.build_tables, t, grid, 1, 256, 0, h->stream));
   h->tables_dirty = false;
   h->main_idle_hint = false;           // the main stream holds work now: partitions that fork next must wait for it
@@ -308,10 +286,10 @@ int ensure_tables(crbm_handle* h) {
 
 // the gather table of the solo grouping follows the parameters lazily: built when a plain chain launch finds it stale
 int ensure_solo_table(crbm_handle* h) {
-  if (h->GS == h->G || h->tf_solo_version == h->params_version) return CRBM_OK;
+  if (h->plan.GS == h->plan.G || h->tf_solo_version == h->params_version) return CRBM_OK;
   TablesArgs t;
   t.W = h->dW; t.b = h->db; t.c = h->dc; t.out = h->d_tf_solo;
-  const unsigned grid = (unsigned)std::max(1, std::min((h->ms_solo.TAB + 255) / 256, h->num_cu * 4));
+  const unsigned grid = (unsigned)std::max(1, std::min((h->plan.ms_solo.TAB + 255) / 256, h->num_cu * 4));
   HIPCHK(jit_launch(h->jk.build_gather_solo, t, grid, 1, 256, 0, h->stream));
   h->tf_solo_version = h->params_version;
   h->main_idle_hint = false;
@@ -328,7 +306,7 @@ BigModel big_model(const crbm_handle* h) {
 
 constexpr int SLAB_FALLBACK = -1000;     // slab_launch_stats / slab_launch_hgv: nothing launched, take the generic kernel
 // free energies of a generic DNA model slab by slab (slab_launch_fe), unless CRBM_SLAB_FE=0 or the slab's tables exceed the LDS
-bool slab_fe_on(const crbm_handle* h) { return h->slab && tab_bytes(h->slab) <= 160 * 1024 && env_int("CRBM_SLAB_FE", 1) != 0; }
+bool slab_fe_on(const crbm_handle* h) { return h->slab.K && tab_bytes(h->slab.ms) <= 160 * 1024 && env_int("CRBM_SLAB_FE", 1) != 0; }
 int slab_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int mode, unsigned long long* ones, uint32_t* masks,
                     uint32_t kind, uint32_t step, uint32_t seq_offset, hipStream_t st);
 int slab_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool data_half, hipStream_t st, ReduceArgs* reduce);
@@ -337,7 +315,7 @@ int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe
 // h | v on packed rows: dense outputs (API), a count of sampled ones (evaluateData) or the masks of one strand (chain)
 int big_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int mode, float* act, float* prob, float* sample,
                    unsigned long long* ones, uint32_t* masks, uint32_t kind, uint32_t step, uint32_t seq_offset, hipStream_t st) {
-  if (h->slab && h->slab_hgv && (masks || ones) && !act && !prob && !sample) {
+  if (h->slab.K && h->slab_hgv && (masks || ones) && !act && !prob && !sample) {
     // the chain's h|v, or the count of a sample (evaluateData, the per-epoch evaluation: into scratch masks): the
     // specialised kernel, slab by slab
     uint32_t* out = masks;
@@ -352,7 +330,7 @@ int big_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int 
   a.m = big_model(h);
   a.letters = d_letters;
   a.n = n; a.L = L; a.Lh = L - h->M + 1; a.LW = lw(h, L);
-  const int pool = h->ms.POOL;
+  const int pool = h->ms().POOL;
   int ks = pool > 1 ? 8 : 32;                                // motifs per staged slab: a divisor of 32 whose filters fit 96 KB
   while (ks > 1 && (size_t)big_hgv_ksp(ks) * h->M * h->A * 4 > 96 * 1024) ks >>= 1;   // (pooled: at most 8, the capacity of big_hgv_pooled_kernel)
   a.KS = ks;
@@ -382,7 +360,7 @@ int big_launch_gibbs(crbm_handle* h, int steps, hipStream_t st) {
   BigVghArgs v;
   v.m = big_model(h);
   v.hm = h->d_hm; v.hmp = h->ds ? h->d_hmp : nullptr; v.vout = h->d_vf;
-  v.nchains = h->B; v.Lf = h->Lf; v.Lv = h->Lv; v.LWs = h->gl.LWs;
+  v.nchains = h->B; v.Lf = h->Lf; v.Lv = h->Lv; v.LWs = h->LWs;
   v.JS = std::max(1, std::min(h->M, (64 * 1024) / (32 * 4 * h->A)));
   // DNA: activations in registers; any other alphabet: one position per thread, activations in LDS (big_vgh_any_kernel)
   const size_t lds = h->A == 4 ? (size_t)v.JS * 32 * 16 + (size_t)BIG_VR * 256 + (size_t)2 * (std::min(BIG_VR * 256, h->Lv) + h->M - 1) * 4   // (+ one mask word of both strands for a chunk)
@@ -405,10 +383,24 @@ int big_launch_gibbs(crbm_handle* h, int steps, hipStream_t st) {
   return CRBM_OK;
 }
 
+// the column reduction of `nrows` partial rows of `row` floats -- the statistic sums of n sequences -- into the data
+// or the model half of d_sums
+ReduceArgs reduce_args(const crbm_handle* h, bool data_half, float* partials, int nrows, int row, int n) {
+  ReduceArgs r;
+  r.partials = partials;
+  r.nrows = nrows; r.row = row;
+  r.K = h->K; r.KAM = h->KAM; r.ds = h->ds; r.want_sparsity = data_half ? 1 : 0;
+  r.sums = h->d_sums + (data_half ? h->sl.data_off : h->sl.model_off);
+  r.skip_begin = data_half ? row : h->sl.model_skip_begin;      // (sw, sb are not carried for the model half)
+  r.skip_len = data_half ? 0 : h->sl.model_skip_len;
+  r.n_value = (float)n;
+  return r;
+}
+
 // raw statistic sums of (letters, n, L) into partial rows; the column reduction is handed back like launch_stats does
 // (reduce->row == 0: nothing left to reduce -- the slabbed form below has written the sums itself)
 int big_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool data_half, hipStream_t st, ReduceArgs* reduce) {
-  if (h->slab) {
+  if (h->slab.K) {
     const int rc = slab_launch_stats(h, d_letters, n, L, data_half, st, reduce);
     if (rc != SLAB_FALLBACK) return rc;
   }
@@ -420,7 +412,7 @@ int big_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bo
   a.n = n; a.L = L; a.Lh = L - M + 1; a.LW = lw(h, L);
   a.want_sparsity = data_half ? 1 : 0;
   a.R = std::max(1, std::min(n, std::max(1, (h->num_cu * 8) / K)));
-  a.pool = h->ms.POOL;
+  a.pool = h->ms().POOL;
   a.CH = std::max(64, std::min(4096, a.Lh));
   a.CH = std::max(a.pool, a.CH - a.CH % a.pool);            // chunks start on pooling-group boundaries
   a.row = 3 * KAM + 3 * K + h->A;
@@ -434,18 +426,7 @@ int big_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bo
   ARGCHK(lds <= 160 * 1024, "motif_length too large for the statistics kernel");
   hipLaunchKernelGGL(big_stats_kernel, dim3(K, a.R), dim3(256), lds, st, a);
   HIPCHK(hipGetLastError());
-  ReduceArgs& r = *reduce;
-  r.partials = pbuf.p;
-  r.nrows = a.R; r.row = a.row;
-  r.K = K; r.KAM = KAM; r.ds = h->ds; r.want_sparsity = a.want_sparsity;
-  if (data_half) {
-    r.sums = h->d_sums + h->sl.data_off;
-    r.skip_begin = a.row; r.skip_len = 0;
-  } else {
-    r.sums = h->d_sums + h->sl.model_off;
-    r.skip_begin = h->sl.model_skip_begin; r.skip_len = h->sl.model_skip_len;
-  }
-  r.n_value = (float)n;
+  *reduce = reduce_args(h, data_half, pbuf.p, a.R, a.row, n);
   return CRBM_OK;
 }
 
@@ -461,7 +442,7 @@ int big_launch_eval(crbm_handle* h, const uint32_t* rows, int n, int L, int hits
   a.m = big_model(h);
   a.letters = rows;
   a.n = n; a.L = L; a.Lh = L - h->M + 1; a.LW = lw(h, L);
-  a.fe = fe; a.fem = fem; a.hmax = hmax; a.hmean = hmean; a.pos_fx = pos_fx; a.hits = hits; a.pool = h->ms.POOL;
+  a.fe = fe; a.fem = fem; a.hmax = hmax; a.hmean = hmean; a.pos_fx = pos_fx; a.hits = hits; a.pool = h->ms().POOL;
   const size_t lds = (((size_t)h->A * h->M + 3) & ~(size_t)3) * 4 + 64 + (size_t)L;
   ARGCHK(lds <= 160 * 1024, "sequence too long for the evaluation kernel of a model of this size");
   hipLaunchKernelGGL(big_eval_kernel, dim3(std::max(1, std::min(n, h->num_cu * 8))), dim3(256), lds, st, a);
@@ -491,7 +472,7 @@ int check_flags(crbm_handle* h) {
 
 int launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int mode, float* act, float* prob,
                float* sample, unsigned long long* ones, uint32_t kind, uint32_t step, uint32_t seq_offset) {
-  if (h->big) return big_launch_hgv(h, d_letters, n, L, mode, act, prob, sample, ones, nullptr, kind, step, seq_offset, h->stream);
+  if (h->big()) return big_launch_hgv(h, d_letters, n, L, mode, act, prob, sample, ones, nullptr, kind, step, seq_offset, h->stream);
   int rc = ensure_tables(h);
   if (rc) return rc;
   HgvArgs a;
@@ -506,30 +487,24 @@ int launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int mode
   a.kind = kind;
   const int ntiles = (n + a.TS - 1) / a.TS;
   const unsigned gx = (unsigned)std::max(1, std::min(ntiles, h->num_cu * 8));
-  HIPCHK(jit_launch(h->jk.hgv, a, gx, 1, 256, (unsigned)tab_bytes(h), h->stream));
+  HIPCHK(jit_launch(h->jk.hgv, a, gx, 1, 256, (unsigned)tab_bytes(h->ms()), h->stream));
   return CRBM_OK;
-}
-
-void use_variant(crbm_handle* h, int v) {
-  h->variant = v;
-  h->gl = h->glv[v];
-  h->gibbs_threads = h->threadsv[v];
-  h->gibbs_grid = h->gridv[v];
 }
 
 StatsGeom stats_geom(const StatsMfmaLayout& st, float* partials, long ngroups, int lds_bytes);
 
-// Arguments of a Gibbs launch of `steps` steps.  model_reduce != null selects the STATS variant: the
+// Arguments of a Gibbs launch of `steps` steps in geometry `g`.  model_reduce != null selects the STATS variant: the
 // launch also leaves the model half of the gradient statistics as one partial row per block in
-// h->partials2 and the column reduction is handed back through `model_reduce`.
-int prepare_gibbs(crbm_handle* h, int steps, ReduceArgs* model_reduce, GibbsArgs* out, unsigned* lds_out) {
-  const bool with_stats = model_reduce != nullptr;
+// h->partials2 (sized here: all this writes to the handle) and the column reduction is handed back
+// through `model_reduce`.  The caller that launches sets h->nset_slots.
+int prepare_gibbs(crbm_handle* h, const ChainGeom& g, int steps, ReduceArgs* model_reduce, GibbsArgs* out, unsigned* lds_out) {
+  const GibbsLayout& gl = g.gl;
   GibbsArgs& a = *out;
   a.tables = h->d_tables;
   a.tables_tf = nullptr; a.off_ws = 0;
   a.hm = h->d_hm; a.hmp = h->ds ? h->d_hmp : nullptr; a.vout = h->d_vf;
-  a.nchains = h->B; a.Lf = h->Lf; a.Lv = h->gl.Lv; a.S = h->gl.S;
-  a.nvb = h->gl.nvb; a.nhb = h->gl.nhb; a.Lrow = h->gl.Lrow; a.LWs = h->gl.LWs;
+  a.nchains = h->B; a.Lf = h->Lf; a.Lv = gl.Lv; a.S = gl.S;
+  a.nvb = gl.nvb; a.nhb = gl.nhb; a.Lrow = gl.Lrow; a.LWs = gl.LWs;
   a.divVB = make_fastdiv((uint32_t)a.nvb);
   a.divHB = make_fastdiv((uint32_t)a.nhb);
   a.divRow = make_fastdiv((uint32_t)(a.Lrow * h->NW));
@@ -540,24 +515,17 @@ int prepare_gibbs(crbm_handle* h, int steps, ReduceArgs* model_reduce, GibbsArgs
   a.clock = h->probe_on ? h->d_probe : nullptr;
   a.timeline = nullptr;
   a.debug = env_int("CRBM_GIBBS_DEBUG", 0);
-  h->nset_slots = h->gibbs_grid * (h->gibbs_threads / 64);
-  a.nblocks = h->gibbs_grid;
+  a.nblocks = g.grid;
   a.stats_off = 0;
   a.sg = StatsGeom();
-  unsigned lds = (unsigned)h->gl.lds_bytes;
-  if (with_stats) {
-    const StatsMfmaLayout st = stats_mfma_layout(h->ms, 0, h->Lf, h->gibbs_threads, 0, false);
-    HIPCHK(h->partials2.ensure((size_t)h->gibbs_grid * st.row));
-    a.stats_off = (h->gl.lds_bytes / 4 + 3) & ~3;
+  unsigned lds = (unsigned)gl.lds_bytes;
+  if (model_reduce) {
+    const StatsMfmaLayout st = stats_mfma_layout(h->ms(), 0, h->Lf, g.threads, 0, false);
+    HIPCHK(h->partials2.ensure((size_t)g.grid * st.row));
+    a.stats_off = (gl.lds_bytes / 4 + 3) & ~3;
     lds = (unsigned)std::max((a.stats_off + st.region_floats) * 4, st.combine_bytes);
-    a.sg = stats_geom(st, h->partials2.p, (long)h->gl.S * st.GPC, (int)lds);
-    ReduceArgs& r = *model_reduce;
-    r.partials = h->partials2.p;
-    r.nrows = h->gibbs_grid; r.row = st.row;
-    r.K = h->K; r.KAM = h->KAM; r.ds = h->ds; r.want_sparsity = 0;
-    r.sums = h->d_sums + h->sl.model_off;
-    r.skip_begin = h->sl.model_skip_begin; r.skip_len = h->sl.model_skip_len;
-    r.n_value = (float)h->B;
+    a.sg = stats_geom(st, h->partials2.p, (long)gl.S * st.GPC, (int)lds);
+    *model_reduce = reduce_args(h, false, h->partials2.p, g.grid, st.row, h->B);
   }
   *lds_out = lds;
   return CRBM_OK;
@@ -596,7 +564,7 @@ void part_worker_main(PartWorker* w) {
 
 // every launch handed to the partitions' threads has been enqueued on its stream
 int drain_part_workers(crbm_handle* h) {
-  for (int p = 1; p < h->chain_parts; ++p) {
+  for (int p = 1; p < h->plan.chain_parts; ++p) {
     PartWorker* w = h->part_worker[p];
     if (!w) continue;
     std::unique_lock<std::mutex> lock(w->mu);
@@ -617,7 +585,7 @@ int join_parts(crbm_handle* h) {
     const int rc = drain_part_workers(h);
     if (rc) return rc;
   }
-  for (int p = 1; p < h->chain_parts; ++p) {          // (partition 0 is the main stream itself)
+  for (int p = 1; p < h->plan.chain_parts; ++p) {          // (partition 0 is the main stream itself)
     HIPCHK(hipEventRecord(h->part_done[p], h->part_stream[p]));
     HIPCHK(hipStreamWaitEvent(h->stream, h->part_done[p], 0));
   }
@@ -625,7 +593,7 @@ int join_parts(crbm_handle* h) {
   return CRBM_OK;
 }
 
-// `steps` Gibbs steps of all chains as chain_parts launches on the partition streams (see crbm_handle::chain_parts)
+// `steps` Gibbs steps of all chains as chain_parts launches on the partition streams (see LaunchPlan::chain_parts)
 int launch_gibbs_parts(crbm_handle* h, int steps) {
   bool first_of_fork = false;
   double stagger_ticks = 0.0;      // first launch after a fork: partition p starts p times this late
@@ -633,7 +601,7 @@ int launch_gibbs_parts(crbm_handle* h, int steps) {
     if (!h->main_idle_hint && hipStreamQuery(h->stream) != hipSuccess) {     // ... unless it is idle: nothing to wait for, no cross-stream dependency to resolve
       (void)hipGetLastError();
       HIPCHK(hipEventRecord(h->ev_parts_fork, h->stream));
-      for (int p = 1; p < h->chain_parts; ++p) HIPCHK(hipStreamWaitEvent(h->part_stream[p], h->ev_parts_fork, 0));
+      for (int p = 1; p < h->plan.chain_parts; ++p) HIPCHK(hipStreamWaitEvent(h->part_stream[p], h->ev_parts_fork, 0));
     }
     h->main_idle_hint = false;
     h->forked = true;
@@ -648,23 +616,20 @@ int launch_gibbs_parts(crbm_handle* h, int steps) {
       // (before the first measurement: ~1 ns per hidden unit and Gibbs step, what configs #2 and #5 run at)
       const double est = h->part_launch_us > 0.0 ? h->part_launch_us
                                                  : 1e-3 * (double)h->B * h->Lf * h->K * (1 + h->ds) * steps;
-      stagger_ticks = 0.9 * est / h->chain_parts * (h->wall_khz / 1000.0);
+      stagger_ticks = 0.9 * est / h->plan.chain_parts * (h->wall_khz / 1000.0);
     }
   }
+  const LaunchPlan& plan = h->plan;
   GibbsArgs a;
   unsigned lds = 0;
-  const GibbsLayout gl_keep = h->gl;
-  const int threads_keep = h->gibbs_threads, grid_keep = h->gibbs_grid;
-  h->gl = h->gl_part; h->gibbs_threads = h->part_threads; h->gibbs_grid = h->part_grid;
-  int rc = prepare_gibbs(h, steps, nullptr, &a, &lds);
-  const unsigned grid = (unsigned)h->gibbs_grid, threads = (unsigned)h->gibbs_threads;
-  h->gl = gl_keep; h->gibbs_threads = threads_keep; h->gibbs_grid = grid_keep;
+  const int rc = prepare_gibbs(h, plan.part, steps, nullptr, &a, &lds);
   if (rc) return rc;
+  const unsigned grid = (unsigned)plan.part.grid, threads = (unsigned)plan.part.threads;
   const size_t per = (size_t)h->Lf * h->NW;
   const int waves = (int)threads / 64;
-  h->nset_slots = h->chain_parts * (int)grid * waves;
-  for (int p = 0; p < h->chain_parts; ++p) {
-    const int c0 = p * h->part_chains, n = std::min(h->part_chains, h->B - c0);
+  h->nset_slots = plan.chain_parts * (int)grid * waves;
+  for (int p = 0; p < plan.chain_parts; ++p) {
+    const int c0 = p * plan.part_chains, n = std::min(plan.part_chains, h->B - c0);
     if (n <= 0) break;
     GibbsArgs ap = a;
     ap.hm = a.hm + (size_t)c0 * per;
@@ -702,27 +667,24 @@ int launch_gibbs_parts(crbm_handle* h, int steps) {
 // partitions; the chain launch inside a training step is followed at once by kernels that wait for all of it and stays whole
 int launch_gibbs(crbm_handle* h, int steps, hipStream_t s = nullptr, ReduceArgs* model_reduce = nullptr, bool plain = false) {
   if (!s) s = h->stream;
-  if (h->big) return big_launch_gibbs(h, steps, s);
+  if (h->big()) return big_launch_gibbs(h, steps, s);
   int rc = ensure_tables(h);
   if (rc) return rc;
-  if (plain && !model_reduce && h->variant == 1 && h->chain_parts > 1 && s == h->stream) return launch_gibbs_parts(h, steps);
+  if (plain && !model_reduce && h->variant == 1 && h->plan.chain_parts > 1 && s == h->stream) return launch_gibbs_parts(h, steps);
+  // (a launch with statistics is the fused variant's, in the model's own geometry)
+  const ChainGeom& g = model_reduce ? h->plan.chain[h->variant] : plain_geom(h->plan, h->variant, false);
   GibbsArgs a;
   unsigned lds = 0;
-  const bool solo = !model_reduce && h->variant == 1 && h->solo_threads > 0;
-  const GibbsLayout gl_keep = h->gl;
-  const int threads_keep = h->gibbs_threads, grid_keep = h->gibbs_grid;
-  if (solo) { h->gl = h->gl_solo; h->gibbs_threads = h->solo_threads; h->gibbs_grid = h->solo_grid; }
-  rc = prepare_gibbs(h, steps, model_reduce, &a, &lds);
-  if (!model_reduce && h->variant == 1 && h->GS != h->G) {     // crbm_gibbs_sparse is compiled for the solo grouping
-    a.tables_tf = h->d_tf_solo; a.off_ws = h->ms.OFF_WS;
+  rc = prepare_gibbs(h, g, steps, model_reduce, &a, &lds);
+  if (!model_reduce && h->variant == 1 && h->plan.GS != h->plan.G) {     // crbm_gibbs_sparse is compiled for the solo grouping
+    a.tables_tf = h->d_tf_solo; a.off_ws = h->ms().OFF_WS;
     if (rc == CRBM_OK) rc = ensure_solo_table(h);
   }
-  const unsigned grid = (unsigned)h->gibbs_grid, threads = (unsigned)h->gibbs_threads;
-  if (solo) { h->gl = gl_keep; h->gibbs_threads = threads_keep; h->gibbs_grid = grid_keep; }
   if (rc) return rc;
+  h->nset_slots = g.grid * (g.threads / 64);
   if (plain && h->d_timeline && h->timeline_next < h->timeline_cap) a.timeline = h->d_timeline + 2 * (size_t)(h->timeline_next++);
   hipFunction_t fn = model_reduce ? h->jk.gibbs_sparse_stats : (h->variant ? h->jk.gibbs_sparse : h->jk.gibbs);
-  HIPCHK(jit_launch(fn, a, grid, 1, threads, lds, s));
+  HIPCHK(jit_launch(fn, a, (unsigned)g.grid, 1, (unsigned)g.threads, lds, s));
   h->gibbs_step += (uint32_t)steps;
   h->launches_since_read += 1;
   return CRBM_OK;
@@ -735,7 +697,7 @@ int launch_gibbs(crbm_handle* h, int steps, hipStream_t s = nullptr, ReduceArgs*
 // chains -- rounds identically and draws identical samples.
 int refresh_activity(crbm_handle* h) {
   if (h->launches_since_read == 0) return CRBM_OK;
-  if (h->big) {          // the last step's h|v launches counted into d_ones
+  if (h->big()) {          // the last step's h|v launches counted into d_ones
     unsigned long long on = 0;
     HIPCHK(hipMemcpy(&on, h->d_ones, sizeof(on), hipMemcpyDeviceToHost));
     h->launches_since_read = 0;
@@ -764,21 +726,22 @@ StatsGeom stats_geom(const StatsMfmaLayout& st, float* partials, long ngroups, i
   return g;
 }
 
-// Arguments of the MFMA statistics kernel (stats_mfma_body) for (letters, n, L): raw statistic sums ->
-// partial rows of the data or the model half.  `threads` 0: the kernel's own block size and the byte
-// LUT; otherwise the geometry of a host kernel it rides in (nibble LUT).
-int prepare_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool data_half, int threads,
-                  StatsMfmaArgs* out, int* lds_out, int* grid_out, int* block_out, ReduceArgs* reduce) {
-  DevBuf<float>& pbuf = data_half ? h->partials : h->partials2;
+// Arguments and launch geometry of the MFMA statistics kernel (stats_mfma_body) of model `ms` with table image `tables`
+// for (letters, n, L): raw statistic sums -> partial rows of the data or the model half in `pbuf`, sized here.  `threads`
+// 0: the kernel's own block size and the byte LUT; otherwise the geometry of a host kernel it rides in (nibble LUT).
+// The column reduction of the rows is the caller's (reduce_args).
+struct StatsLaunch { int lds = 0, grid = 0, block = 0, row = 0; };   // (row: floats per partial row, `grid` rows)
+int prepare_stats(crbm_handle* h, const ModelShape& ms, const float* tables, DevBuf<float>& pbuf, const uint32_t* d_letters, int n, int L,
+                  bool data_half, int threads, StatsMfmaArgs* out, StatsLaunch* launch) {
   const int want_sp = data_half ? 1 : 0;
-  const int Lh = L - h->M + 1;
-  const int tabs = tab_bytes(h);
+  const int Lh = L - ms.M + 1;
+  const int tabs = tab_bytes(ms);
   const bool own = threads <= 0;
   // CRBM_STATS_MAX_TILES is an experiment knob: it must come with CRBM_JIT_DEFINES=-DCRBM_STATS_MAX_TILES=<same>
-  const StatsMfmaLayout st = stats_mfma_layout(h->ms, want_sp, Lh, own ? env_int("CRBM_STATS_THREADS", 0) : threads, tabs, own,
+  const StatsMfmaLayout st = stats_mfma_layout(ms, want_sp, Lh, own ? env_int("CRBM_STATS_THREADS", 0) : threads, tabs, own,
                                                env_int("CRBM_STATS_MAX_TILES", CRBM_STATS_MAX_TILES));
   StatsMfmaArgs& a = *out;
-  a.tables = h->d_tables;
+  a.tables = tables;
   a.letters = d_letters;
   a.n = n; a.L = L; a.Lh = Lh; a.LW = lw(h, L);
   const long ngroups = (long)n * st.GPC;
@@ -801,24 +764,12 @@ int prepare_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool 
   HIPCHK(pbuf.ensure((size_t)gx * st.row));
   a.nblocks = gx;
   a.sg = stats_geom(st, pbuf.p, ngroups, lds);
-  *lds_out = lds; *grid_out = gx; *block_out = st.threads;
-  ReduceArgs& r = *reduce;
-  r.partials = pbuf.p;
-  r.nrows = gx; r.row = st.row;
-  r.K = h->K; r.KAM = h->KAM; r.ds = h->ds; r.want_sparsity = want_sp;
-  if (data_half) {
-    r.sums = h->d_sums + h->sl.data_off;
-    r.skip_begin = st.row; r.skip_len = 0;
-  } else {
-    r.sums = h->d_sums + h->sl.model_off;
-    r.skip_begin = h->sl.model_skip_begin; r.skip_len = h->sl.model_skip_len;
-  }
-  r.n_value = (float)n;
+  launch->lds = lds; launch->grid = gx; launch->block = st.threads; launch->row = st.row;
   return CRBM_OK;
 }
 
 // The statistics of a generic DNA model (motif_length <= 64) on the matrix cores.  VH[k], H[k] and the sparsity sums of motif
-// k depend on that motif's filter alone, so the model is a row of independent sub-models of `slab->K` motifs: the
+// k depend on that motif's filter alone, so the model is a row of independent sub-models of `slab.K` motifs: the
 // specialised statistics kernel of that sub-model (stats_mfma_body: gather table in LDS, P split into f16 halves,
 // v_mfma_f32_16x16x32_f16) runs once per slab on the slab's own table image -- W and b of a slab are contiguous pieces of
 // the model's (K,4,M) and (K) arrays -- and slab_reduce_kernel adds the slab's partial rows into its columns of d_sums.
@@ -828,20 +779,20 @@ int prepare_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool 
 // first multiple of ten at or behind K - Ks (sampler groups are ten units wide: every unit keeps its group and field), so it
 // overlaps its neighbour and may reach up to nine motifs past K -- into the zero padding of W and b (crbm_create)
 int slab_origin(const crbm_handle* h, int i) {
-  const int Ks = h->slab->K;
+  const int Ks = h->slab.K;
   if ((i + 1) * Ks <= h->K) return i * Ks;
   return h->slab_hgv ? ((h->K - Ks + 9) / 10) * 10 : h->K - Ks;
 }
 
 SlabPlan slab_plan(const crbm_handle* h) {
   SlabPlan p;
-  p.Ks = h->slab->K; p.K = h->K; p.last_k0 = slab_origin(h, h->slab_n - 1);
+  p.Ks = h->slab.K; p.K = h->K; p.last_k0 = slab_origin(h, h->slab_n - 1);
   return p;
 }
 
 // one launch builds the table images of all slabs (blockIdx.y = slab: slab_tables_body)
 int slab_ensure_tables(crbm_handle* h, hipStream_t st) {
-  crbm_handle* s = h->slab;
+  const SlabModel* s = &h->slab;
   if (h->slab_tables_version == h->params_version) return CRBM_OK;
   SlabTablesArgs a;
   a.t.W = h->dW; a.t.b = h->db; a.t.c = h->dc; a.t.out = h->d_slab_tables;
@@ -859,9 +810,9 @@ int slab_ensure_tables(crbm_handle* h, hipStream_t st) {
 // (HgvMasksArgs::masks, atomicOr: neighbouring slabs share words).
 int slab_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int mode, unsigned long long* ones, uint32_t* masks,
                     uint32_t kind, uint32_t step, uint32_t seq_offset, hipStream_t st) {
-  crbm_handle* s = h->slab;
+  const SlabModel* s = &h->slab;
   const int Lh = L - h->M + 1;
-  if (tab_bytes(s) > 160 * 1024) return SLAB_FALLBACK;
+  if (tab_bytes(s->ms) > 160 * 1024) return SLAB_FALLBACK;
   int rc = slab_ensure_tables(h, st);
   if (rc) return rc;
   HIPCHK(hipMemsetAsync(masks, 0, (size_t)n * Lh * h->NW * sizeof(uint32_t), st));
@@ -883,7 +834,7 @@ int slab_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int
   sa.table_stride = s->ms.TABLES_ALL;
   const int ntiles = (n + a.TS - 1) / a.TS;
   const unsigned gx = (unsigned)std::max(1, std::min(ntiles, h->num_cu * 8));
-  HIPCHK(jit_launch(s->jk.slab_hgv, sa, gx, (unsigned)h->slab_n, 256, (unsigned)tab_bytes(s), st));
+  HIPCHK(jit_launch(s->jk.slab_hgv, sa, gx, (unsigned)h->slab_n, 256, (unsigned)tab_bytes(s->ms), st));
   return CRBM_OK;
 }
 
@@ -891,32 +842,30 @@ int slab_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int
 // (blockIdx.y = slab: its table image, its partial rows), then slab_reduce_kernel -- one launch too -- reduces every slab's
 // partial rows into the slab's columns of the model's sums.
 int slab_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool data_half, hipStream_t st, ReduceArgs* reduce) {
-  crbm_handle* s = h->slab;
+  SlabModel* s = &h->slab;
   const int Ks = s->K, M = h->M;
-  s->err.clear();
-  {
-    const int trc = slab_ensure_tables(h, st);
-    if (trc) return trc;
-  }
-  s->d_tables = h->d_slab_tables;
-  SlabStatsArgs sa;
-  ReduceArgs r;
-  int lds = 0, gx = 0, block = 0;
-  const int rc = prepare_stats(s, d_letters, n, L, data_half, 0, &sa.a, &lds, &gx, &block, &r);
-  if (rc == CRBM_ERR_INVALID) return SLAB_FALLBACK;      // (a data set whose rows the slab kernel's LDS does not take)
-  if (rc) return fail(h, rc, "slabbed statistics: " + s->err);
+  int rc = slab_ensure_tables(h, st);
+  if (rc) return rc;
   DevBuf<float>& pbuf = data_half ? s->partials : s->partials2;
-  const size_t per_slab = (size_t)r.nrows * r.row;
+  SlabStatsArgs sa;
+  StatsLaunch l;
+  rc = prepare_stats(h, s->ms, h->d_slab_tables, pbuf, d_letters, n, L, data_half, 0, &sa.a, &l);
+  if (rc == CRBM_ERR_INVALID) {      // (a data set whose rows the slab kernel's LDS does not take)
+    h->err.clear();
+    return SLAB_FALLBACK;
+  }
+  if (rc) return fail(h, rc, "slabbed statistics: " + h->err);
+  const size_t per_slab = (size_t)l.grid * l.row;
   HIPCHK(pbuf.ensure(per_slab * h->slab_n));
   sa.a.sg.partials = pbuf.p;
   sa.table_stride = s->ms.TABLES_ALL; sa.pad_ = 0;
   sa.partial_stride = (long long)per_slab;
-  if (jit_launch(data_half ? s->jk.slab_stats_data : s->jk.slab_stats_model, sa, (unsigned)gx, (unsigned)h->slab_n, (unsigned)block, (unsigned)lds, st) != hipSuccess)
+  if (jit_launch(data_half ? s->jk.slab_stats_data : s->jk.slab_stats_model, sa, (unsigned)l.grid, (unsigned)h->slab_n, (unsigned)l.block, (unsigned)l.lds, st) != hipSuccess)
     return fail(h, CRBM_ERR_HIP, "launch of the slab statistics kernel failed");
   SlabReduceArgs ra;
   ra.partials = pbuf.p;
   ra.sums = h->d_sums + (data_half ? h->sl.data_off : h->sl.model_off);
-  ra.nrows = r.nrows; ra.row = r.row;
+  ra.nrows = l.grid; ra.row = l.row;
   ra.Ks = Ks; ra.k0 = slab_origin(h, h->slab_n - 1); ra.K = h->K; ra.M4 = 4 * M;
   ra.partial_stride = (long long)per_slab;
   ra.ds = h->ds; ra.want_sparsity = data_half ? 1 : 0;
@@ -933,11 +882,11 @@ int slab_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, b
 
 // Free energies of a generic DNA model (freeEnergy, evaluateData, the per-epoch evaluation of fit(): convRBM.py:657-697, :517-522):
 // the slab model's free-energy kernel leaves every slab's per-motif terms in a scratch (one launch, blockIdx.y = slab),
-// slab_fe_combine_kernel adds them up per sequence.  The scratch belongs to the caller's stream (the shadow handle's out_b
-// for the main stream, out_b2 for the second stream of a host-input sweep): the two streams' slabs run at the same time.
+// slab_fe_combine_kernel adds them up per sequence.  The scratch belongs to the caller's stream (SlabModel::fe_scratch: [0]
+// for the main stream, [1] for the second stream of a host-input sweep): the two streams' slabs run at the same time.
 int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe, float* fem, DevBuf<float>* scratch, hipStream_t st) {
-  crbm_handle* s = h->slab;
-  if (tab_bytes(s) > 160 * 1024) return SLAB_FALLBACK;
+  const SlabModel* s = &h->slab;
+  if (tab_bytes(s->ms) > 160 * 1024) return SLAB_FALLBACK;
   int rc = slab_ensure_tables(h, st);
   if (rc) return rc;
   const size_t per_slab = (size_t)n * s->K;
@@ -950,7 +899,7 @@ int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe
   sa.table_stride = s->ms.TABLES_ALL; sa.pad_ = 0;
   sa.fem_stride = (long long)per_slab;
   const unsigned gx = (unsigned)std::max(1, std::min((n + 3) / 4, h->num_cu * 8));
-  HIPCHK(jit_launch(s->jk.slab_fe, sa, gx, (unsigned)h->slab_n, 256, (unsigned)tab_bytes(s), st));
+  HIPCHK(jit_launch(s->jk.slab_fe, sa, gx, (unsigned)h->slab_n, 256, (unsigned)tab_bytes(s->ms), st));
   SlabFeCombineArgs ca;
   ca.scratch = scratch->p;
   ca.c_log2e = h->d_slab_tables + s->ms.OFF_C;
@@ -963,86 +912,37 @@ int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe
   return CRBM_OK;
 }
 
-// The slab model of a generic DNA model: up to `want` motifs are one slab, a larger model takes slabs of a multiple of ten
-// motifs (the sampler's groups); the largest candidate whose statistics kernel fits the LDS.  Returns 0 motifs when none does.
-int slab_choose(int K, int M, int ds, int pool, int Lf, int* G_out, ModelShape* ms_out) {
-  const int want = std::max(10, std::min(env_int("CRBM_SLAB_MOTIFS", 60), 64));      // (the slab kernels are compiled for models of up to 64 motifs: crbm_jit.h)
-  const int first = K <= want ? K : want / 10 * 10;
-  for (int cand : {first, 40, 30, 20, 10}) {
-    if (cand > K || (cand != first && cand >= first)) continue;
-    int G = env_int("CRBM_SLAB_GROUP", 0);
-    if (G < 1 || G > 4) {
-      // the table budget of the specialised kernels; long motifs that it leaves with single letters take pairs where those fit
-      // twice 48 KB (60 x 40 double-stranded: 77 KB, training step 1.55 -> 1.19 ms at 2048 chains; a larger budget for ALL slabs
-      // costs the statistics kernel waves: 256 x 4 double-stranded 1.72 -> 1.99 ms)
-      const int budget = env_int("CRBM_SLAB_TABLE_BUDGET", 26 * 1024);
-      G = choose_group(cand, M, ds, budget);
-      if (G == 1) G = choose_group(cand, M, ds, std::max(budget, 48 * 1024));
-    }
-    const ModelShape ms = model_shape(cand, M, ds, G, pool);
-    bool fit = true;
-    for (int want_sp = 0; want_sp <= 1 && fit; ++want_sp) {
-      const int tabs = ms.TAB * 4;
-      const StatsMfmaLayout st = stats_mfma_layout(ms, want_sp, Lf, 0, tabs, true);
-      if (st.threads > 1024 || std::max(st.region_floats * 4 + tabs, st.combine_bytes) > 160 * 1024) fit = false;
-    }
-    if (fit) { *G_out = G; *ms_out = ms; return cand; }
-  }
-  return 0;
-}
-
-// The shadow handle of the slab model of a generic handle (crbm_create); leaves h->slab null, with the reason in
-// h->slab_note, when the model is not one for slabs.  CRBM_SLAB_STATS=0 switches them off (A/B runs, tests).
-int slab_setup(crbm_handle* h) {
-  if (!h->big) return CRBM_OK;
-  if (env_int("CRBM_SLAB_STATS", 1) == 0) { h->slab_note = "CRBM_SLAB_STATS=0"; return CRBM_OK; }
-  if (h->A != 4 || h->M > MAX_MOTIF_LENGTH) { h->slab_note = "other alphabet, or motifs beyond 64 letters"; return CRBM_OK; }
-  int G = 0;
-  ModelShape ms;
-  const int Ks = slab_choose(h->K, h->M, h->ds, h->ms.POOL, h->Lf, &G, &ms);
-  if (!Ks) { h->slab_note = "no slab of this motif length fits the LDS"; return CRBM_OK; }
-  crbm_handle* s = new crbm_handle();
-  std::string err;
-  if (jit_load(Ks, h->M, h->ds, G, G, ms.POOL, 0, 256, &s->jk, &err, true) != 0) {
-    h->slab_note = "kernel specialisation of the slab failed: " + err;
-    if (s->jk.module) (void)hipModuleUnload(s->jk.module);
-    delete s;
-    return CRBM_OK;
-  }
-  s->cfg = h->cfg; s->cfg.num_motifs = Ks;
-  s->K = Ks; s->M = h->M; s->ds = h->ds; s->A = 4; s->G = G; s->GS = G; s->KAM = Ks * 4 * h->M;
-  s->ms = ms; s->ms_solo = ms; s->NW = ms.NW;
-  s->Lf = h->Lf; s->Lv = h->Lv; s->B = h->B;
-  s->device = h->device; s->num_cu = h->num_cu;
-  s->stream = h->stream;                 // borrowed: never destroyed through the shadow
-  s->big = false; s->tables_dirty = false;
-  s->sl = sums_layout(Ks, h->M);
-  s->stats_rows = h->stats_rows;
-  h->slab_n = (h->K + Ks - 1) / Ks;
-  h->slab_hgv = (h->slab_n == 1 || Ks % 10 == 0) && env_int("CRBM_SLAB_HGV", 1) != 0;
-  if (hipMalloc((void**)&s->d_sums, (size_t)s->sl.count * 4) != hipSuccess ||
-      hipMalloc((void**)&h->d_slab_tables, (size_t)h->slab_n * ms.TABLES_ALL * 4) != hipSuccess) {
-    (void)hipGetLastError();
-    if (s->d_sums) (void)hipFree(s->d_sums);
-    if (h->d_slab_tables) { (void)hipFree(h->d_slab_tables); h->d_slab_tables = nullptr; }
-    (void)hipModuleUnload(s->jk.module);
-    delete s;
-    h->slab_note = "no memory for the slab tables";
-    return CRBM_OK;
-  }
-  h->slab = s;
-  return CRBM_OK;
-}
-
 void slab_destroy(crbm_handle* h) {
-  if (crbm_handle* s = h->slab) {
-    if (s->d_sums) (void)hipFree(s->d_sums);
-    s->partials.release(); s->partials2.release(); s->out_b.release(); s->out_b2.release();
-    if (s->jk.module) (void)hipModuleUnload(s->jk.module);
-    delete s;
-    h->slab = nullptr;
-  }
+  SlabModel* s = &h->slab;
+  s->partials.release(); s->partials2.release(); s->fe_scratch[0].release(); s->fe_scratch[1].release();
+  if (s->jk.module) (void)hipModuleUnload(s->jk.module);
+  s->jk = JitKernels();
   if (h->d_slab_tables) { (void)hipFree(h->d_slab_tables); h->d_slab_tables = nullptr; }
+}
+
+// The slab model of a generic handle (crbm_create), as the plan chose it; leaves h->slab.K zero, with the reason in
+// h->slab_note, when the model is not one for slabs or the slab's kernels or tables are not to be had.
+void slab_setup(crbm_handle* h) {
+  const LaunchPlan& plan = h->plan;
+  if (!plan.big) return;
+  if (!plan.slab_K) { h->slab_note = plan.slab_note; return; }
+  const int n = (h->K + plan.slab_K - 1) / plan.slab_K;
+  std::string err;
+  if (jit_load(plan.slab_K, h->M, h->ds, plan.slab_G, plan.slab_G, plan.slab_ms.POOL, 0, 256, &h->slab.jk, &err, true) != 0) {
+    slab_destroy(h);
+    h->slab_note = "kernel specialisation of the slab failed: " + err;
+    return;
+  }
+  if (hipMalloc((void**)&h->d_slab_tables, (size_t)n * plan.slab_ms.TABLES_ALL * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    h->d_slab_tables = nullptr;
+    slab_destroy(h);
+    h->slab_note = "no memory for the slab tables";
+    return;
+  }
+  h->slab.K = plan.slab_K; h->slab.ms = plan.slab_ms;
+  h->slab_n = n;
+  h->slab_hgv = (n == 1 || plan.slab_K % 10 == 0) && env_int("CRBM_SLAB_HGV", 1) != 0;
 }
 
 // stand-alone launch; the column reduction is handed back to the caller (`defer`, to pair it with the
@@ -1052,14 +952,16 @@ int launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool d
   if (!s) s = h->stream;
   int rc = ensure_tables(h);
   if (rc) return rc;
-  StatsMfmaArgs a;
   ReduceArgs r;
-  int lds = 0, gx = 0, block = 0;
-  if (h->big) rc = big_launch_stats(h, d_letters, n, L, data_half, s, &r);
+  if (h->big()) rc = big_launch_stats(h, d_letters, n, L, data_half, s, &r);
   else {
-    rc = prepare_stats(h, d_letters, n, L, data_half, 0, &a, &lds, &gx, &block, &r);
+    StatsMfmaArgs a;
+    StatsLaunch l;
+    DevBuf<float>& pbuf = data_half ? h->partials : h->partials2;
+    rc = prepare_stats(h, h->ms(), h->d_tables, pbuf, d_letters, n, L, data_half, 0, &a, &l);
     if (rc) return rc;
-    rc = jit_launch(data_half ? h->jk.stats_mfma_data : h->jk.stats_mfma_model, a, (unsigned)gx, 1, (unsigned)block, (unsigned)lds, s) == hipSuccess
+    r = reduce_args(h, data_half, pbuf.p, l.grid, l.row, n);
+    rc = jit_launch(data_half ? h->jk.stats_mfma_data : h->jk.stats_mfma_model, a, (unsigned)l.grid, 1, (unsigned)l.block, (unsigned)l.lds, s) == hipSuccess
              ? CRBM_OK : fail(h, CRBM_ERR_HIP, "launch of the statistics kernel failed");
   }
   if (rc) return rc;
@@ -1095,7 +997,7 @@ void swap_param_sets(crbm_handle* h) {
 int launch_update(crbm_handle* h, int L_data) {
   UpdateTablesArgs a;
   fill_update_args(h, L_data, a);
-  if (h->big) {        // element-wise and in place: no table images to rebuild, no second buffer set
+  if (h->big()) {        // element-wise and in place: no table images to rebuild, no second buffer set
     UpdateArgs& u = a.u;
     u.oW = h->dW; u.ob = h->db; u.oc = h->dc; u.ovW = h->dvW; u.ovb = h->dvb; u.ovc = h->dvc;
     hipLaunchKernelGGL(big_update_kernel, dim3(grid_for((long)h->KAM + h->K + h->A, 256, h->num_cu * 4)), dim3(256), 0, h->stream, u);
@@ -1103,7 +1005,7 @@ int launch_update(crbm_handle* h, int L_data) {
     h->params_version += 1;
     return CRBM_OK;
   }
-  const unsigned grid = (unsigned)std::max(1, std::min((h->ms.TABLES_ALL + 4095) / 4096, 32));
+  const unsigned grid = (unsigned)std::max(1, std::min((h->ms().TABLES_ALL + 4095) / 4096, 32));
   HIPCHK(jit_launch(h->jk.update_tables, a, grid, 1, UPDATE_THREADS, (unsigned)((h->KAM + h->K + 4) * 4), h->stream));
   swap_param_sets(h);
   return CRBM_OK;
@@ -1153,7 +1055,7 @@ int launch_reduce_pair(crbm_handle* h, ReducePair pair, bool publish) {
 int train_local_dev(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool publish = false) {
   int rc = ensure_tables(h);
   if (rc) return rc;
-  if (h->slab) {      // the slab tables too, on the main stream: both halves read them (CRBM_OVERLAP: from two streams)
+  if (h->slab.K) {      // the slab tables too, on the main stream: both halves read them (CRBM_OVERLAP: from two streams)
     rc = slab_ensure_tables(h, h->stream);
     if (rc) return rc;
   }
@@ -1167,18 +1069,21 @@ int train_local_dev(crbm_handle* h, const uint32_t* d_letters, int n, int L, boo
   const bool paired = !h->overlap && n > 0;
   if (h->fuse_stats && paired && h->one_launch) {
     // the whole local phase in one launch (train_local_body): chain + model half in the first
-    // gibbs_grid blocks, data half in the blocks behind them
+    // g.grid blocks, data half in the blocks behind them
+    const ChainGeom& g = h->plan.chain[h->variant];
     TrainLocalArgs t;
     unsigned glds = 0;
-    rc = prepare_gibbs(h, h->cfg.cd_k, &pair.half[1], &t.g, &glds);
+    rc = prepare_gibbs(h, g, h->cfg.cd_k, &pair.half[1], &t.g, &glds);
     if (rc) return rc;
-    int dlds = 0, dgrid = 0, dblock = 0;
-    rc = prepare_stats(h, d_letters, n, L, true, h->gibbs_threads, &t.d, &dlds, &dgrid, &dblock, &pair.half[0]);
+    StatsLaunch d;
+    rc = prepare_stats(h, h->ms(), h->d_tables, h->partials, d_letters, n, L, true, g.threads, &t.d, &d);
     if (rc) return rc;
-    const unsigned lds = std::max(glds, (unsigned)dlds);
+    pair.half[0] = reduce_args(h, true, h->partials.p, d.grid, d.row, n);
+    const unsigned lds = std::max(glds, (unsigned)d.lds);
     t.g.sg.lds_floats = (int)(lds / 4);
     t.d.sg.lds_floats = (int)(lds / 4);
-    HIPCHK(jit_launch(h->jk.train_local, t, (unsigned)(h->gibbs_grid + dgrid), 1, (unsigned)h->gibbs_threads, lds, h->stream));
+    h->nset_slots = g.grid * (g.threads / 64);
+    HIPCHK(jit_launch(h->jk.train_local, t, (unsigned)(g.grid + d.grid), 1, (unsigned)g.threads, lds, h->stream));
     h->gibbs_step += (uint32_t)h->cfg.cd_k;
     h->launches_since_read += 1;
     return launch_reduce_pair(h, pair, publish);
@@ -1278,7 +1183,7 @@ int launch_ipc_allreduce_update(crbm_handle* h, int L_data) {
   a.ipc.status = ipc_status_of(h->ipc_buf, h);
   a.ipc.expect = value; a.ipc.nranks = h->nranks; a.ipc.count = h->sl.count;
   a.ipc.timeout_ticks = h->ipc_timeout_ticks;
-  const unsigned grid = (unsigned)std::max(1, std::min((h->ms.TABLES_ALL + 4095) / 4096, 32));
+  const unsigned grid = (unsigned)std::max(1, std::min((h->ms().TABLES_ALL + 4095) / 4096, 32));
   // the new parameters and one word (update_tables_ipc_body): the published sums are read where they lie, not staged
   const unsigned lds = (unsigned)((h->KAM + h->K + 4 + 4) * 4);
   HIPCHK(jit_launch(h->jk.update_tables_ipc, a, grid, 1, UPDATE_THREADS, lds, h->stream));
@@ -1316,7 +1221,7 @@ int check_data_shape(crbm_handle* h, int n, int L) {
   ARGCHK(L >= h->M, "sequence length must be >= motif_length");
   ARGCHK((long)L * 4 < (1 << 20), "sequence too long");
   // the reference reshapes the hidden layer into (…, Lh / pooling, pooling) (convRBM.py:250-252); fit() truncates for it
-  ARGCHK((L - h->M + 1) % h->ms.POOL == 0, "hidden length L - motif_length + 1 must be a multiple of pooling");
+  ARGCHK((L - h->M + 1) % h->ms().POOL == 0, "hidden length L - motif_length + 1 must be a multiple of pooling");
   return CRBM_OK;
 }
 
@@ -1349,7 +1254,7 @@ static RowSource host_codes_(const uint8_t* c, int n, int L, int A) { RowSource 
 //      the sweep starts (an ensure() inside the loop then finds its buffer large enough);
 //   3. a slab's outputs are copied from the set that produced them, on that set's stream.
 // Everything a slab writes belongs to its set and is reached through sweep_set: staging and letters, the outputs oa / ob,
-// the per-motif scratch of the slabbed free energies (in the slab model's shadow handle), the features' own buffers.
+// the per-motif scratch of the slabbed free energies (SlabModel::fe_scratch), the features' own buffers.
 // Set 0 is the handle's main stream and buffers, which the calls outside the sweeps use as well.  What the two streams
 // share is read-only during a sweep (parameters, d_tables and d_slab_tables: sweep_begin builds them first) or combined
 // in any order (d_flags: atomicOr; the hit summary's position sums: 64-bit integer atomics).
@@ -1359,13 +1264,12 @@ struct SweepSet {
   DevBuf<uint32_t>* letters;
   DevBuf<float>* oa;
   DevBuf<float>* ob;
-  DevBuf<float>* fe_scratch;
+  DevBuf<float>* fe_scratch;    // of the slab model: never null, but only to be used behind slab_fe_on(h) -- a handle without a slab model has nothing that fills it
   crbm_handle::SetBufs* own;
 };
 SweepSet sweep_set(crbm_handle* h, int i) {
-  crbm_handle* s = h->slab;
-  if (i & 1) return SweepSet{h->stream2, &h->stage2, &h->letters2, &h->out_a2, &h->out_b2, s ? &s->out_b2 : nullptr, &h->set_bufs[1]};
-  return SweepSet{h->stream, &h->stage, &h->letters, &h->out_a, &h->out_b, s ? &s->out_b : nullptr, &h->set_bufs[0]};
+  if (i & 1) return SweepSet{h->stream2, &h->stage2, &h->letters2, &h->out_a2, &h->out_b2, &h->slab.fe_scratch[1], &h->set_bufs[1]};
+  return SweepSet{h->stream, &h->stage, &h->letters, &h->out_a, &h->out_b, &h->slab.fe_scratch[0], &h->set_bufs[0]};
 }
 
 // enqueue on the set's stream: rows [start, start+cnt) of a host source, through the set's staging buffer, as packed
@@ -1426,7 +1330,7 @@ int sweep_slab(const RowSource& src, size_t out_bytes_per_row) {
 int sweep_begin(crbm_handle* h) {
   int rc = ensure_tables(h);
   if (rc) return rc;
-  if (h->slab) {
+  if (h->slab.K) {
     rc = slab_ensure_tables(h, h->stream);
     if (rc) return rc;
   }
@@ -1519,132 +1423,6 @@ int validate_config(const crbm_config* cfg) {
   return CRBM_OK;
 }
 
-// Gibbs launch geometry.  A thread owns 4 consecutive positions, a block owns
-// tiles of S whole chains (grid-stride).  Pick (S, threads) that keeps lanes
-// busy in both phases and splits the tiles evenly over the CUs.
-struct GibbsGeom {
-  int S, threads, grid, lds;
-};
-
-// solo: geometry of launches that only advance the chains (crbm_gibbs_steps*, the chain launch of models
-// whose statistics run in kernels of their own): free of the 256-thread build of the fused variants.
-GibbsGeom choose_gibbs_geometry(const ModelShape& ms, int Lf, int B, int num_cu, bool sparse, bool solo = false) {
-  const int forceS = env_int("CRBM_GIBBS_S", 0), forceT = env_int("CRBM_GIBBS_THREADS", 0);
-  GibbsGeom best{1, 256, 1, 0};
-  double best_score = -1.0;
-  // 256 first: larger blocks (one table copy shared by up to 16 waves; the chain kernels are then compiled
-  // with that launch bound) win only where they score strictly better -- models whose tables leave room
-  // for fewer than four 256-thread blocks per CU.  The fused statistics variants are built for 256.
-  double best_occupancy = 0.0;
-  for (int threads : {256, 128, 64, 512, 1024}) {
-    // measured: config #4 (two 256-thread blocks per CU) 2.62 -> 2.26 ms per launch with one 1024-thread
-    // block; config #5 (three blocks per CU) is no faster with two 512-thread blocks -- so only when the
-    // small blocks reach at most half the waves
-    // Solo launches of single-stranded models take the large blocks whenever they score better (config #2:
-    // one 1024-thread block of 32 chains per CU 22.7 us per launch against 23.8 with four 256-thread blocks:
-    // one table copy per CU, and the short last round of the v|h pass spreads over all SIMDs).  Double-stranded
-    // models too since they gather from one table and their queue of undecided units holds 254 entries
-    // (config #5: 158 us per launch with three 256-thread blocks of 3 chains per CU, 145 with two 512-thread
-    // blocks of 8, 143.6 with one 1024-thread block of 16 -- 147 when the queue overflows at 62 entries).
-    const bool big_ok = solo ? true : (!ms.FUSE_STATS && best_occupancy <= 0.5);
-    // (experiment: CRBM_FUSED_THREADS=512 with CRBM_JIT_DEFINES=-DCRBM_FUSED_TB=512 gives the fused training launch larger blocks)
-    const int fusedT = (!solo && ms.FUSE_STATS) ? env_int("CRBM_FUSED_THREADS", 0) : 0;
-    if (fusedT > 0 && threads != fusedT) continue;
-    if (fusedT == 0 && threads > 256 && (!big_ok || env_int("CRBM_GIBBS_MAX_THREADS", 1024) < threads)) continue;
-    if (forceT > 0 && threads != forceT) continue;
-    for (int S = 1; S <= std::min(B, 64); ++S) {
-      if (forceS > 0 && S != forceS) continue;
-      const GibbsLayout gl = gibbs_layout(ms, Lf, S, sparse);
-      if (gl.lds_bytes > 150 * 1024 && !(forceS > 0)) continue;
-      if (gl.lds_bytes > 160 * 1024 || (long)S * gl.Lrow * ms.NW >= (1 << 20)) continue;
-      // lanes are used at wave granularity (an idle wave of a pass costs nothing);
-      // 4 hidden positions cost ~1.5x a 4-position visible block
-      const double iv = (double)S * gl.nvb, ih = (double)S * gl.nhb;
-      const double util = (iv + 0.375 * ih) / (64.0 * (std::ceil(iv / 64.0) + 0.375 * std::ceil(ih / 64.0)));
-      const double ntiles = std::ceil((double)B / S);
-      const double per_cu_tiles = ntiles / num_cu;
-      const double balance = per_cu_tiles / std::ceil(per_cu_tiles);
-      const int blocks_cu = std::max(1, std::min((160 * 1024) / gl.lds_bytes, 1024 / threads));   // <= 16 waves / CU
-      const double waves_cu = std::min(per_cu_tiles, (double)blocks_cu) * std::min((double)threads, iv) / 64.0;
-      const double occupancy = std::min(1.0, waves_cu / 16.0);                // 4 waves / SIMD hide the LDS latency
-      const double score = util * balance * (0.4 + 0.6 * occupancy) - 1e-4 * S;
-      if (score > best_score) {
-        best_score = score;
-        best = GibbsGeom{S, threads, (int)std::min(ntiles, (double)num_cu * blocks_cu), gl.lds_bytes};
-        if (threads <= 256) best_occupancy = occupancy;
-      }
-    }
-  }
-  const int forceG = env_int("CRBM_GIBBS_GRID", 0);
-  if (forceG > 0) best.grid = forceG;
-  return best;
-}
-
-// Partitions of a plain chain launch (crbm_handle::chain_parts).  Worth it where a launch is short and its blocks are
-// small: the partitions' kernels then share every CU (several blocks of each resident at once) and one partition's
-// drain / dispatch / ramp is filled by the other's work.  Measured (two handles of half the chains, alternating launches):
-// config #2 with 256-thread blocks of 8 chains 21.7 -> 17.6 us per step of the whole batch (17.4 with four partitions);
-// with one 1024-thread block per CU per partition nothing (20.5 vs 20.6): the partitions then own disjoint CUs.
-// In the library: config #2 20.3 -> 17.8 us, config #5 137.9 -> 136.1 us, config #4 2191 -> 2180 us (not worth a second
-// geometry there); more partitions do not help (config #2: three 17.8 us against 17.4 with two, four 28 us: a process has
-// four hardware queues, and partitions that share one serialise).
-// Auto: two partitions when the small-block geometry of half the batch puts at least two blocks on a CU, still covers
-// every CU, and a launch is short (by the number of hidden units per step); CRBM_CHAIN_PARTS forces 1..4.
-struct PartPlan {
-  int parts, part_chains;
-  GibbsGeom geom;      // of one partition
-};
-PartPlan plan_chain_parts(const ModelShape& ms, int Lf, int B, int num_cu) {
-  PartPlan one{1, B, GibbsGeom{0, 0, 0, 0}};
-  const int forced = env_int("CRBM_CHAIN_PARTS", 0);
-  if (forced == 1 || B < 2) return one;
-  const int parts = forced >= 2 ? std::min(forced, 4) : 2;
-  // small blocks: the geometry the fused training launch uses (at most 256 threads unless they reach half the waves)
-  const int half = (B + parts - 1) / parts;
-  GibbsGeom g = choose_gibbs_geometry(ms, Lf, half, num_cu, true, false);
-  if (g.lds <= 0) return one;
-  const int tiles = (B + g.S - 1) / g.S, tiles_part = (tiles + parts - 1) / parts;
-  const int blocks_cu = std::max(1, std::min((160 * 1024) / g.lds, 1024 / g.threads));
-  if (forced < 2) {
-    const double items = (double)B * Lf * ms.K * (1 + ms.DS);          // hidden units per step
-    if (blocks_cu < 2 || tiles_part < num_cu || items > 256e6) return one;
-  }
-  if (tiles_part < 1) return one;
-  PartPlan p{parts, tiles_part * g.S, g};
-  p.geom.grid = std::min(tiles_part, num_cu * blocks_cu);
-  // (Measured and NOT adopted: twice the chains per tile where the partition's tiles do not divide over its resident blocks
-  //  -- config #5: 2048 tiles of 2 chains on 768 blocks.  Forced for every kernel of the handle, CRBM_GIBBS_S=4, it runs
-  //  128.6 instead of 135.2 us per step; chosen here for the partitioned launch alone 150.7: the kernel is compiled with the
-  //  occupancy hint of the handle's regular geometry, three blocks per CU, and the larger tiles leave two.)
-  return p;
-}
-
-// Does the model need the generic ("big") kernels?  Beyond 256 motifs or 64 letters the specialised templates do not
-// exist; within them the LDS decides: the chain kernel holds its tables and at least one chain, the statistics kernel a
-// column image per 16 motifs beside the gather table (at most 16 roles of 64 threads).  CRBM_FORCE_BIG=1 puts any
-// model on the generic path -- the tests compare the two paths on the same model with it.
-bool model_needs_big(const ModelShape& ms, int Lf, int B, int num_cu) {
-  if (env_int("CRBM_FORCE_BIG", 0)) return true;
-  if (ms.K > MAX_MOTIFS || ms.M > MAX_MOTIF_LENGTH) return true;
-  if (choose_gibbs_geometry(ms, Lf, B, num_cu, true).lds <= 0) return true;
-  for (int want_sp = 0; want_sp <= 1; ++want_sp) {
-    const int tabs = ms.TAB * 4;
-    const StatsMfmaLayout st = stats_mfma_layout(ms, want_sp, Lf, 0, tabs, true);
-    if (st.threads > 1024 || std::max(st.region_floats * 4 + tabs, st.combine_bytes) > 160 * 1024) return true;
-  }
-  return false;
-}
-
-// waves per SIMD the sparse Gibbs variant reaches with its geometry; 0 when >= 4 (no hint needed)
-int gibbs_block_bound(int threads) { return threads > 512 ? 1024 : threads > 256 ? 512 : 256; }
-
-int gibbs_wpe_hint(const GibbsGeom& g) {
-  if (g.lds <= 0) return 0;
-  const int blocks_cu = std::max(1, std::min((160 * 1024) / g.lds, 2048 / g.threads));
-  const int wpe = std::max(1, blocks_cu * (g.threads / 64) / 4);
-  return wpe < 4 ? wpe : 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1654,39 +1432,18 @@ extern "C" {
 int crbm_precompile(const crbm_config* cfg) {
   int rc = validate_config(cfg);
   if (rc) return rc;
-  const int ds = cfg->doublestranded ? 1 : 0;
-  int G = env_int("CRBM_GROUP", 0);
-  if (G < 1 || G > 4) G = choose_group(cfg->num_motifs, cfg->motif_length, ds, env_int("CRBM_TABLE_BUDGET", 26 * 1024));
-  const ModelShape ms = model_shape(cfg->num_motifs, cfg->motif_length, ds, G, cfg->pooling);
+  // the kernels of the plan crbm_create will derive for this model (on a device of CRBM_NUM_CU compute units, 256 unless set)
+  const LaunchPlan p = plan_launches(cfg->num_motifs, cfg->motif_length, cfg->doublestranded ? 1 : 0, cfg->input_dims, cfg->pooling,
+                                     cfg->fantasy_hidden_len > 0 ? cfg->fantasy_hidden_len : 200, cfg->batchsize, env_int("CRBM_NUM_CU", 256));
   std::vector<char> code;
   bool cached = false;
   std::string file, err;
-  const int Lf_pc = cfg->fantasy_hidden_len > 0 ? cfg->fantasy_hidden_len : 200;
-  const int ncu = env_int("CRBM_NUM_CU", 256);
-  if (cfg->num_motifs > MAX_MOTIFS || cfg->motif_length > MAX_MOTIF_LENGTH || cfg->input_dims != 4 || model_needs_big(ms, Lf_pc, cfg->batchsize, ncu)) {
-    // the generic kernels are compiled ahead of time; a DNA model with motifs of up to 64 letters also takes the kernels of
-    // its slab model (slab_setup): those are specialised
-    if (cfg->input_dims == 4 && cfg->motif_length <= MAX_MOTIF_LENGTH && env_int("CRBM_SLAB_STATS", 1) != 0) {
-      int Gs = 0;
-      ModelShape mss;
-      const int Ks = slab_choose(cfg->num_motifs, cfg->motif_length, ds, cfg->pooling, Lf_pc, &Gs, &mss);
-      if (Ks > 0 && jit_compile(Ks, cfg->motif_length, ds, Gs, Gs, mss.POOL, 0, 256, &code, &cached, &file, &err, true) != 0) {
-        g_create_error = err;
-        return CRBM_ERR_HIP;
-      }
-    }
-    return CRBM_OK;
-  }
-  const GibbsGeom gs = choose_gibbs_geometry(ms, Lf_pc, cfg->batchsize, ncu, true);
-  int tb = gs.threads;
-  if (ms.DENSE) tb = std::max(tb, choose_gibbs_geometry(ms, Lf_pc, cfg->batchsize, ncu, false).threads);
-  const PartPlan plan = plan_chain_parts(ms, Lf_pc, cfg->batchsize, ncu);
-  if (plan.parts > 1) tb = std::max(tb, plan.geom.threads);
-  int GS = plan.parts > 1 ? G : solo_group(ms.K, ms.M, ms.DS, G, ms.POOL);
-  GibbsGeom solo = choose_gibbs_geometry(model_shape(ms.K, ms.M, ms.DS, GS, ms.POOL), Lf_pc, cfg->batchsize, ncu, true, true);
-  if (solo.lds <= 0 && GS != G) { GS = G; solo = choose_gibbs_geometry(ms, Lf_pc, cfg->batchsize, ncu, true, true); }
-  tb = std::max(tb, solo.threads);
-  if (jit_compile(ms.K, ms.M, ms.DS, ms.G, GS, ms.POOL, gibbs_wpe_hint(gs), gibbs_block_bound(tb), &code, &cached, &file, &err) != 0) {
+  int rc_jit = 0;
+  if (!p.big)
+    rc_jit = jit_compile(p.ms.K, p.ms.M, p.ms.DS, p.G, p.GS, p.ms.POOL, p.gibbs_wpe, p.gibbs_tb, &code, &cached, &file, &err);
+  else if (p.slab_K > 0)      // the generic kernels are compiled ahead of time; the kernels of the model's slab model are specialised
+    rc_jit = jit_compile(p.slab_K, p.ms.M, p.ms.DS, p.slab_G, p.slab_G, p.slab_ms.POOL, 0, 256, &code, &cached, &file, &err, true);
+  if (rc_jit != 0) {
     g_create_error = err;
     return CRBM_ERR_HIP;
   }
@@ -1713,11 +1470,6 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
   hh->seed = cfg->seed;
   hh->device = cfg->device;
   hh->sl = sums_layout(hh->K, hh->M, hh->A);
-  // gather-table group size, derived shapes
-  hh->G = env_int("CRBM_GROUP", 0);
-  if (hh->G < 1 || hh->G > 4) hh->G = choose_group(hh->K, hh->M, hh->ds, env_int("CRBM_TABLE_BUDGET", 26 * 1024));
-  hh->ms = model_shape(hh->K, hh->M, hh->ds, hh->G, cfg->pooling);
-  hh->NW = hh->ms.NW;
   auto bail = [&](int code) { crbm_destroy(hh); return code; };
   hipError_t e;
 #define TRY(expr)                                                                                 \
@@ -1734,68 +1486,26 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, hh->device) == hipSuccess && khz > 0) hh->wall_khz = khz;
     (void)hipGetLastError();
   }
-  // (the specialised kernels are DNA kernels: 2-bit letters, tables over letter tuples; any other alphabet is generic)
-  hh->big = (hh->K > MAX_MOTIFS || hh->M > MAX_MOTIF_LENGTH || hh->A != 4) ? true : model_needs_big(hh->ms, hh->Lf, hh->B, hh->num_cu);
-  if (hh->big) {
-    // no specialised kernels, no table images: the state layout is the same (K-bit masks, 2-bit letters)
-    hh->gl = GibbsLayout();
-    hh->gl.S = 1; hh->gl.Lv = hh->Lv; hh->gl.LWs = letter_words_any(hh->A, hh->Lv);
-    hh->glv[0] = hh->glv[1] = hh->gl;
-    hh->variant = 1; hh->topdown_mode = 2;
-    hh->GS = hh->G; hh->ms_solo = hh->ms;
-    hh->chain_parts = 1; hh->part_chains = hh->B;
-    hh->gridv[0] = hh->gridv[1] = 0;
+  // which kernels, launch geometry (crbm_plan.h), then the model-specific kernels (hiprtc; cached on disk)
+  hh->plan = plan_launches(hh->K, hh->M, hh->ds, hh->A, cfg->pooling, hh->Lf, hh->B, hh->num_cu);
+  const LaunchPlan& plan = hh->plan;
+  hh->NW = plan.ms.NW;
+  if (plan.refusal) {
+    g_create_error = plan.refusal;
+    return bail(CRBM_ERR_INVALID);
   }
-  // launch geometry, then the model-specific kernels (hiprtc; cached on disk)
-  hh->has_dense = !hh->big && hh->ms.DENSE != 0;
-  for (int v = hh->has_dense ? 0 : 1; v < 2 && !hh->big; ++v) {
-    const GibbsGeom geom = choose_gibbs_geometry(hh->ms, hh->Lf, hh->B, hh->num_cu, v == 1);
-    if (geom.lds <= 0) {
-      g_create_error = "model too large for the LDS-resident Gibbs kernel";
-      return bail(CRBM_ERR_INVALID);
-    }
-    hh->glv[v] = gibbs_layout(hh->ms, hh->Lf, geom.S, v == 1);
-    if (v == 1) hh->gibbs_wpe = gibbs_wpe_hint(geom);
-    hh->threadsv[v] = geom.threads;
-    hh->gridv[v] = geom.grid;
-  }
-  if (!hh->big) {
-    // plain chain launches: their own geometry; short launches in partitions on streams of their own (chain_parts);
-    // unpartitioned ones of small fused models with their own letter grouping (solo_group)
-    const PartPlan plan = plan_chain_parts(hh->ms, hh->Lf, hh->B, hh->num_cu);
-    hh->chain_parts = plan.parts;
-    hh->part_chains = plan.parts > 1 ? plan.part_chains : hh->B;
-    if (plan.parts > 1) {
-      hh->gl_part = gibbs_layout(hh->ms, hh->Lf, plan.geom.S, true);
-      hh->part_threads = plan.geom.threads;
-      hh->part_grid = plan.geom.grid;
-    }
-    // the unpartitioned launch: its own geometry and, where nothing else launches that kernel, its own letter grouping
-    hh->GS = plan.parts > 1 ? hh->G : solo_group(hh->K, hh->M, hh->ds, hh->G, cfg->pooling);
-    hh->ms_solo = model_shape(hh->K, hh->M, hh->ds, hh->GS, cfg->pooling);
-    GibbsGeom solo = choose_gibbs_geometry(hh->ms_solo, hh->Lf, hh->B, hh->num_cu, true, true);
-    if (solo.lds <= 0 && hh->GS != hh->G) {           // the larger table leaves no room for a chain: the model's grouping
-      hh->GS = hh->G; hh->ms_solo = hh->ms;
-      solo = choose_gibbs_geometry(hh->ms_solo, hh->Lf, hh->B, hh->num_cu, true, true);
-    }
-    if (solo.lds > 0 && (hh->GS != hh->G || solo.threads != hh->threadsv[1] || solo.S != hh->glv[1].S || solo.grid != hh->gridv[1])) {
-      hh->gl_solo = gibbs_layout(hh->ms_solo, hh->Lf, solo.S, true);
-      hh->solo_threads = solo.threads;
-      hh->solo_grid = solo.grid;
-    }
-  }
-  if (!hh->big) {
+  // (generic models: no specialised kernels, no table images; the state layout is the same -- K-bit masks, 2-bit letters)
+  hh->LWs = hh->big() ? letter_words_any(hh->A, hh->Lv) : plan.chain[1].gl.LWs;
+  hh->variant = 1; hh->topdown_mode = 2;
+  if (!hh->big()) {
     // The set-bit walk is the variant of every model (its cost follows the hidden activity,
     // ~2 % under the reference's sparsity target); CRBM_TOPDOWN=dense pins the table variant
     // of small models for A/B runs.  Never switched at run time: the two round differently.
     const char* td = getenv("CRBM_TOPDOWN");
-    hh->topdown_mode = (td && !strcmp(td, "dense") && hh->has_dense) ? 1 : 2;
-    use_variant(hh, hh->topdown_mode == 1 ? 0 : 1);
-  }
-  if (!hh->big) {
+    hh->topdown_mode = (td && !strcmp(td, "dense") && plan.has_dense) ? 1 : 2;
+    hh->variant = hh->topdown_mode == 1 ? 0 : 1;
     std::string err;
-    const int tb = gibbs_block_bound(std::max(std::max(std::max(hh->has_dense ? hh->threadsv[0] : 0, hh->threadsv[1]), hh->solo_threads), hh->part_threads));
-    if (jit_load(hh->K, hh->M, hh->ds, hh->G, hh->GS, hh->ms.POOL, hh->gibbs_wpe, tb, &hh->jk, &err) != 0) {
+    if (jit_load(hh->K, hh->M, hh->ds, plan.G, plan.GS, hh->ms().POOL, plan.gibbs_wpe, plan.gibbs_tb, &hh->jk, &err) != 0) {
       g_create_error = "kernel specialisation failed: " + err;
       return bail(CRBM_ERR_HIP);
     }
@@ -1806,12 +1516,12 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
   TRY(hipEventCreate(&hh->ev1));
   TRY(hipEventCreateWithFlags(&hh->ev_fork, hipEventDisableTiming));
   TRY(hipEventCreateWithFlags(&hh->ev_join, hipEventDisableTiming));
-  if (hh->chain_parts > 1) {
+  if (plan.chain_parts > 1) {
     TRY(hipEventCreateWithFlags(&hh->ev_parts_fork, hipEventDisableTiming));
     TRY(hipEventCreate(&hh->ev_cal0));
     TRY(hipEventCreate(&hh->ev_cal1));
     hh->part_stream[0] = hh->stream;          // partition 0 rides on the handle's own stream: one hardware queue fewer
-    for (int p = 1; p < hh->chain_parts; ++p) {
+    for (int p = 1; p < plan.chain_parts; ++p) {
       TRY(hipStreamCreateWithFlags(&hh->part_stream[p], hipStreamNonBlocking));
       TRY(hipEventCreate(&hh->part_done[p]));     // with timestamps: crbm_time_gibbs reads them
       {
@@ -1826,7 +1536,7 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
   hh->overlap = env_int("CRBM_OVERLAP", 0) != 0;   // measured: no gain once the statistics kernel fills the chip
   // (generic handles: W and b carry ten motifs of zero padding behind motif K -- the last slab of the slabbed kernels
   //  starts on a multiple of ten and may reach past the model's end, slab_origin)
-  const size_t pad_k = hh->big ? 10 : 0;
+  const size_t pad_k = hh->big() ? 10 : 0;
   const size_t kam = (size_t)hh->KAM + pad_k * hh->A * hh->M, k = (size_t)hh->K + pad_k;
   TRY(hipMalloc((void**)&hh->dW, kam * 4)); TRY(hipMalloc((void**)&hh->dvW, kam * 4));
   TRY(hipMalloc((void**)&hh->db, k * 4));   TRY(hipMalloc((void**)&hh->dvb, k * 4));
@@ -1838,17 +1548,21 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
   TRY(hipMalloc((void**)&hh->dW2, kam * 4)); TRY(hipMalloc((void**)&hh->dvW2, kam * 4));
   TRY(hipMalloc((void**)&hh->db2, k * 4));   TRY(hipMalloc((void**)&hh->dvb2, k * 4));
   TRY(hipMalloc((void**)&hh->dc2, cb));      TRY(hipMalloc((void**)&hh->dvc2, cb));
-  TRY(hipMalloc((void**)&hh->d_tables, hh->big ? 64 : (size_t)hh->ms.TABLES_ALL * 4));
-  if (hh->GS != hh->G) TRY(hipMalloc((void**)&hh->d_tf_solo, (size_t)hh->ms_solo.TAB * 4));
+  TRY(hipMalloc((void**)&hh->d_tables, hh->big() ? 64 : (size_t)hh->ms().TABLES_ALL * 4));
+  if (plan.GS != plan.G) TRY(hipMalloc((void**)&hh->d_tf_solo, (size_t)plan.ms_solo.TAB * 4));
   const size_t mwords = (size_t)hh->B * hh->Lf * hh->NW;
   TRY(hipMalloc((void**)&hh->d_hm, mwords * 4)); TRY(hipMemset(hh->d_hm, 0, mwords * 4));
   TRY(hipMalloc((void**)&hh->d_hmp, mwords * 4)); TRY(hipMemset(hh->d_hmp, 0, mwords * 4));
-  const size_t vwords = (size_t)hh->B * hh->gl.LWs;
+  const size_t vwords = (size_t)hh->B * hh->LWs;
   TRY(hipMalloc((void**)&hh->d_vf, vwords * 4)); TRY(hipMemset(hh->d_vf, 0, vwords * 4));
   TRY(hipMalloc((void**)&hh->d_flags, 16)); TRY(hipMemset(hh->d_flags, 0, 16));
   TRY(hipMalloc((void**)&hh->d_ones, 16)); TRY(hipMemset(hh->d_ones, 0, 16));
   {
-    const size_t slots = (size_t)std::max(std::max(hh->gridv[0] * (hh->threadsv[0] / 64), hh->gridv[1] * (hh->threadsv[1] / 64)), std::max(hh->solo_grid * (hh->solo_threads / 64), hh->chain_parts * hh->part_grid * (hh->part_threads / 64))) + 64;
+    // one slot per wave of the largest launch; a partitioned launch is chain_parts launches of the partition's geometry
+    size_t slots = plan.part.on() ? (size_t)plan.chain_parts * plan.part.grid * (plan.part.threads / 64) : 0;
+    for (const ChainGeom* g : {&plan.chain[0], &plan.chain[1], &plan.solo})
+      if (g->on()) slots = std::max(slots, (size_t)g->grid * (g->threads / 64));
+    slots += 64;
     TRY(hipMalloc((void**)&hh->d_nset, slots * 4)); TRY(hipMemset(hh->d_nset, 0, slots * 4));
   }
   TRY(hipMalloc((void**)&hh->d_sums, (size_t)hh->sl.count * 4)); TRY(hipMemset(hh->d_sums, 0, (size_t)hh->sl.count * 4));
@@ -1861,11 +1575,12 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
   hh->tables_dirty = true;
   {
     const char* sv = getenv("CRBM_STATS");
-    hh->fuse_stats = !hh->big && hh->ms.FUSE_STATS && hh->variant == 1 && !(sv && !strcmp(sv, "split"));
+    hh->fuse_stats = !hh->big() && hh->ms().FUSE_STATS && hh->variant == 1 && !(sv && !strcmp(sv, "split"));
     hh->one_launch = !(sv && !strcmp(sv, "two"));
     if (hh->fuse_stats) {   // the fused launch appends the statistics slices to the chain image: it must fit the LDS
-      const StatsMfmaLayout st = stats_mfma_layout(hh->ms, 0, hh->Lf, hh->gibbs_threads, 0, false);
-      const int lds = std::max((((hh->gl.lds_bytes / 4 + 3) & ~3) + st.region_floats) * 4, st.combine_bytes);
+      const ChainGeom& g = plan.chain[hh->variant];
+      const StatsMfmaLayout st = stats_mfma_layout(hh->ms(), 0, hh->Lf, g.threads, 0, false);
+      const int lds = std::max((((g.gl.lds_bytes / 4 + 3) & ~3) + st.region_floats) * 4, st.combine_bytes);
       if (lds > 160 * 1024) hh->fuse_stats = false;
     }
   }
@@ -2026,7 +1741,7 @@ int crbm_get_fantasy_visible(crbm_handle* h, float* v) {
   const size_t count = (size_t)h->B * h->A * h->Lv;
   HIPCHK(h->stage.ensure(count));
   DecodeArgs a;
-  a.letters = h->d_vf; a.v = h->stage.p; a.n = h->B; a.L = h->Lv; a.LW = h->gl.LWs; a.A = h->A;
+  a.letters = h->d_vf; a.v = h->stage.p; a.n = h->B; a.L = h->Lv; a.LW = h->LWs; a.A = h->A;
   if (h->A == 4) hipLaunchKernelGGL(decode_onehot_kernel, dim3(grid_for((long)h->B * h->Lv, 256, h->num_cu * 8)), dim3(256), 0, h->stream, a);
   else hipLaunchKernelGGL(decode_onehot_any_kernel, dim3(grid_for((long)h->B * h->Lv, 256, h->num_cu * 8)), dim3(256), 0, h->stream, a);
   HIPCHK(hipGetLastError());
@@ -2231,7 +1946,7 @@ int crbm_time_gibbs(crbm_handle* h, int32_t k, int32_t launches, float* total_ms
   h->probe_on = true;
   const bool want_timeline = env_int("CRBM_GIBBS_TIMELINE", 0) != 0 && launches <= 4096;
   if (want_timeline) {
-    const int need = launches * std::max(1, h->chain_parts);
+    const int need = launches * std::max(1, h->plan.chain_parts);
     if (need > h->timeline_cap) {
       if (h->d_timeline) (void)hipFree(h->d_timeline);
       h->d_timeline = nullptr;
@@ -2254,7 +1969,7 @@ int crbm_time_gibbs(crbm_handle* h, int32_t k, int32_t launches, float* total_ms
       unsigned long long t0 = ~0ull;
       for (size_t i = 0; i < t.size(); i += 2) if (t[i]) t0 = std::min(t0, t[i]);
       const double us = 1000.0 / h->wall_khz;
-      fprintf(stderr, "chain launches (block 0: start-end in us from the first start; %d partition(s), launch order):", h->chain_parts);
+      fprintf(stderr, "chain launches (block 0: start-end in us from the first start; %d partition(s), launch order):", h->plan.chain_parts);
       for (size_t i = 0; i < t.size(); i += 2) {
         if (i == 2 * 60 && t.size() > 2 * 120) { fprintf(stderr, " ..."); i = t.size() - 2 * 60; }
         fprintf(stderr, " %.1f-%.1f", (t[i] - t0) * us, (t[i + 1] - t0) * us);
@@ -2292,10 +2007,10 @@ int crbm_time_gibbs(crbm_handle* h, int32_t k, int32_t launches, float* total_ms
       if (rc) return rc;
     }
     HIPCHK(hipEventRecord(h->ev1, h->stream));                       // partition 0 = the main stream
-    for (int p = 1; p < h->chain_parts; ++p) HIPCHK(hipEventRecord(h->part_done[p], h->part_stream[p]));
+    for (int p = 1; p < h->plan.chain_parts; ++p) HIPCHK(hipEventRecord(h->part_done[p], h->part_stream[p]));
     HIPCHK(spin_until(h->ev1));
     HIPCHK(hipEventElapsedTime(&worst, h->ev0, h->ev1));
-    for (int p = 1; p < h->chain_parts; ++p) {
+    for (int p = 1; p < h->plan.chain_parts; ++p) {
       float ms = 0.f;
       HIPCHK(spin_until(h->part_done[p]));
       HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->part_done[p]));
@@ -2440,14 +2155,14 @@ int launch_free_energy(crbm_handle* h, const uint32_t* rows, int n, int L, const
   if (rc) return rc;
   HIPCHK(set.oa->ensure((size_t)n));
   HIPCHK(set.ob->ensure((size_t)n * h->K));
-  if (h->big) return big_launch_eval(h, rows, n, L, 0, set.oa->p, set.ob->p, nullptr, nullptr, nullptr, set.fe_scratch, set.st);
+  if (h->big()) return big_launch_eval(h, rows, n, L, 0, set.oa->p, set.ob->p, nullptr, nullptr, nullptr, set.fe_scratch, set.st);
   FeArgs a;
   a.tables = h->d_tables;
   a.letters = rows;
   a.n = n; a.L = L; a.Lh = L - h->M + 1; a.LW = lw(h, L);
   a.fe = set.oa->p; a.fem = set.ob->p;
   const unsigned gx = (unsigned)std::max(1, std::min((n + 3) / 4, h->num_cu * 8));
-  HIPCHK(jit_launch(h->jk.free_energy, a, gx, 1, 256, (unsigned)tab_bytes(h), set.st));
+  HIPCHK(jit_launch(h->jk.free_energy, a, gx, 1, 256, (unsigned)tab_bytes(h->ms()), set.st));
   return CRBM_OK;
 }
 
@@ -2461,7 +2176,7 @@ int free_energy_any(crbm_handle* h, const RowSource& src, float* fe, float* fem)
     const SweepSet set = sweep_set(h, i);
     HIPCHK(set.oa->ensure((size_t)slab));
     HIPCHK(set.ob->ensure((size_t)slab * K));
-    if (slab_fe_on(h)) HIPCHK(set.fe_scratch->ensure((size_t)slab * h->slab->K * h->slab_n));
+    if (slab_fe_on(h)) HIPCHK(set.fe_scratch->ensure((size_t)slab * h->slab.K * h->slab_n));
   }
   return sweep_run(h, src, slab, 2,
     [&](const SweepSet& set, const uint32_t* rows, int, int cnt) -> int { return launch_free_energy(h, rows, cnt, src.L, set); },
@@ -2508,12 +2223,12 @@ int hit_summary_any(crbm_handle* h, const RowSource& src, float* hmax, float* hm
   int rc = check_data_shape(h, src.n, src.L);
   if (rc) return rc;
   const int n = src.n, L = src.L, Lh = L - h->M + 1, K = h->K;
-  const int tabs = h->big ? 0 : tab_bytes(h);
+  const int tabs = h->big() ? 0 : tab_bytes(h->ms());
   // a block covers one chunk of 64*HIT_NI positions; its (PC,K) sums share the LDS with the tables
-  const int PC = 64 * h->ms.HIT_NI;
-  const int nchunks = h->big ? 1 : (Lh + PC - 1) / PC;           // (the big path's kernel takes a whole sequence per block)
+  const int PC = 64 * h->ms().HIT_NI;
+  const int nchunks = h->big() ? 1 : (Lh + PC - 1) / PC;           // (the big path's kernel takes a whole sequence per block)
   const unsigned lds = (unsigned)(tabs + (size_t)PC * K * 8);    // tables + the block's fixed-point position sums
-  ARGCHK(h->big || lds <= 160u * 1024u, "model too large for the hit-summary kernel");
+  ARGCHK(h->big() || lds <= 160u * 1024u, "model too large for the hit-summary kernel");
   // sums over sequences per (motif, position): 64-bit fixed point (HIT_FX units), so that the order in which blocks,
   // slabs and the two streams add does not show in the result
   unsigned long long* pos_fx = nullptr;
@@ -2546,7 +2261,7 @@ int hit_summary_any(crbm_handle* h, const RowSource& src, float* hmax, float* hm
       a.inv_Lh = 1.0f / (float)Lh;
       a.pos_fx = pos_fx;                          // both streams add (integers: any order)
       const unsigned gx = (unsigned)std::max(1, std::min((cnt + 3) / 4, std::max(1, h->num_cu * 8 / nchunks)));
-      if (h->big) {
+      if (h->big()) {
         const int r = big_launch_eval(h, rows, cnt, L, 1, nullptr, nullptr, a.hmax, a.hsum, pos_fx, nullptr, set.st);
         if (r) return r;
       } else
@@ -2597,7 +2312,7 @@ void sort_sites(const std::vector<SiteRec>& in, int nrows, std::vector<SiteRec>*
 }
 
 // Thresholded sites and best sites over a source, a two-stream sweep.  Specialised models: the fused crbm_motif_sites
-// pass (motif_sites_body).  Generic models (h->big): the dense h|v of hit_probs_any into the set's outputs (oa: the
+// pass (motif_sites_body).  Generic models (h->big()): the dense h|v of hit_probs_any into the set's outputs (oa: the
 // forward strand, or sigma(x + x') single-stranded; ob: the reverse-complemented filter), then motif_sites_select_kernel.
 // Every set owns its records, counter and keys (sized before the sweep); a slab whose count exceeds its set's record
 // buffer is run again into a larger one before anything is copied (its rows are still in the set's buffers: the set is
@@ -2612,13 +2327,13 @@ int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64
   int rc = check_data_shape(h, src.n, src.L);
   if (rc) return rc;
   const int n = src.n, L = src.L, Lh = L - h->M + 1, K = h->K, S = h->ds ? 2 : 1;
-  const int PC = 64 * h->ms.HIT_NI;
-  const int nchunks = h->big ? 1 : (Lh + PC - 1) / PC;
-  const unsigned lds = h->big ? 0u : (unsigned)tab_bytes(h);
-  ARGCHK(h->big || lds <= 160u * 1024u, "model too large for the motif-site kernel");
+  const int PC = 64 * h->ms().HIT_NI;
+  const int nchunks = h->big() ? 1 : (Lh + PC - 1) / PC;
+  const unsigned lds = h->big() ? 0u : (unsigned)tab_bytes(h->ms());
+  ARGCHK(h->big() || lds <= 160u * 1024u, "model too large for the motif-site kernel");
   rc = sweep_begin(h);
   if (rc) return rc;
-  const size_t dense_per_row = h->big ? (size_t)S * K * Lh * sizeof(float) : 0;
+  const size_t dense_per_row = h->big() ? (size_t)S * K * Lh * sizeof(float) : 0;
   const int slab = sweep_slab(src, (size_t)K * 8 + dense_per_row);
   const size_t rec0 = std::min((size_t)slab * K * S * Lh, std::max<size_t>((size_t)1 << 16, (size_t)4 * slab * K));
   for (int i = 0; i < (slab < n ? 2 : 1); ++i) {        // everything both streams write, at its size, before either starts
@@ -2628,7 +2343,7 @@ int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64
       HIPCHK(set.own->site_count.ensure(1));
     }
     if (want_best) HIPCHK(set.own->site_keys.ensure((size_t)slab * K));
-    if (h->big) {
+    if (h->big()) {
       HIPCHK(set.oa->ensure((size_t)slab * K * Lh));
       if (S == 2) HIPCHK(set.ob->ensure((size_t)slab * K * Lh));
     }
@@ -2641,7 +2356,7 @@ int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64
     o.best = want_best ? set.own->site_keys.p : nullptr;
     o.threshold = threshold;
     if (want_recs) HIPCHK(hipMemsetAsync(o.count, 0, sizeof(unsigned long long), set.st));
-    if (h->big) {
+    if (h->big()) {
       // convRBM.py:507-514 as hit_probs_any: doublestranded -> sigma(x) (and the flipped filter), else sigma(x + x')
       int r = big_launch_hgv(h, rows, cnt, L, h->ds ? 0 : 2, nullptr, set.oa->p, nullptr, nullptr, nullptr, KIND_API_H, 0, 0, set.st);
       if (!r && S == 2) r = big_launch_hgv(h, rows, cnt, L, 1, nullptr, set.ob->p, nullptr, nullptr, nullptr, KIND_API_H, 0, 0, set.st);
@@ -2732,13 +2447,15 @@ int scan_sites_any(crbm_handle* h, const uint8_t* codes, int64_t T, float thresh
   ARGCHK(T >= 0 && T <= (int64_t)INT32_MAX, "stream length must lie in [0, 2^31 - 1] (start is 32 bits wide)");
   ARGCHK(codes || T == 0, "null argument");
   ARGCHK(h->A == 4, "crbm_scan_sites_codes: the alphabet must be DNA's (input_dims == 4)");
-  ARGCHK(h->ms.POOL == 1, "crbm_scan_sites_codes: pooling > 1 is not supported (pool groups have no anchor in a stream)");
-  crbm_handle* km = h->big ? h->slab : h;          // whose kernel runs: the model's own, or that of its slab model
-  ARGCHK(km && tab_bytes(km) <= 160 * 1024, "crbm_scan_sites_codes: models that run on the generic kernels alone (motifs beyond 64 letters) are not supported");
+  ARGCHK(h->ms().POOL == 1, "crbm_scan_sites_codes: pooling > 1 is not supported (pool groups have no anchor in a stream)");
+  // whose kernel runs: the model's own, or that of its slab model
+  const ModelShape& kms = h->big() ? h->slab.ms : h->ms();
+  const JitKernels& kjk = h->big() ? h->slab.jk : h->jk;
+  ARGCHK((!h->big() || h->slab.K) && tab_bytes(kms) <= 160 * 1024, "crbm_scan_sites_codes: models that run on the generic kernels alone (motifs beyond 64 letters) are not supported");
   *count = 0;
   const int M = h->M, S = h->ds ? 2 : 1;
   if (T < M) return CRBM_OK;
-  const int starts_all = (int)(T - M + 1), nslab = h->big ? h->slab_n : 1;
+  const int starts_all = (int)(T - M + 1), nslab = h->big() ? h->slab_n : 1;
   int rc = sweep_begin(h);
   if (rc) return rc;
   // a window start costs its staged byte, its letter and validity bits, per slab its counts and offsets, and a share of records
@@ -2758,7 +2475,7 @@ int scan_sites_any(crbm_handle* h, const uint8_t* codes, int64_t T, float thresh
     HIPCHK(set.own->scan_tiles.ensure((size_t)nslab * lay.tiles));
     HIPCHK(set.own->scan_off.ensure((size_t)nslab * lay.tiles + nslab));
     if (want_recs) {
-      rcap[i] = (size_t)std::min<unsigned long long>({(unsigned long long)capacity, (unsigned long long)seg * km->K * S,
+      rcap[i] = (size_t)std::min<unsigned long long>({(unsigned long long)capacity, (unsigned long long)seg * kms.K * S,
                                                      std::max<unsigned long long>(1ull << 16, (unsigned long long)seg / 4)});
       HIPCHK(set.own->site_recs.ensure(rcap[i] * nslab));
     }
@@ -2766,20 +2483,20 @@ int scan_sites_any(crbm_handle* h, const uint8_t* codes, int64_t T, float thresh
   auto scan_args = [&](const SweepSet& set, int si, int start, int cnt, int pass) {
     const ScanLayout l = scan_layout((long)cnt + M - 1, cnt);
     ScanArgs a;
-    a.tables = h->big ? h->d_slab_tables : h->d_tables;
+    a.tables = h->big() ? h->d_slab_tables : h->d_tables;
     a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
     a.lane_cnt = set.own->scan_lanes.p; a.tile_cnt = set.own->scan_tiles.p; a.tile_off = set.own->scan_off.p;
     a.recs = set.own->site_recs.p; a.capacity = rcap[si];
     a.starts = cnt; a.tiles = l.tiles; a.pos0 = start; a.pass = pass; a.threshold = threshold;
-    a.table_stride = km->ms.TABLES_ALL;
-    if (h->big) a.plan = slab_plan(h);
+    a.table_stride = kms.TABLES_ALL;
+    if (h->big()) a.plan = slab_plan(h);
     else { a.plan.Ks = h->K; a.plan.K = h->K; a.plan.last_k0 = 0; }
     return a;
   };
   auto launch_pass = [&](const SweepSet& set, int si, int start, int cnt, int pass) -> int {
     const ScanArgs a = scan_args(set, si, start, cnt, pass);
     const unsigned gx = (unsigned)std::max(1, std::min((a.tiles + 3) / 4, std::max(1, h->num_cu * 8 / nslab)));
-    HIPCHK(jit_launch(km->jk.scan_sites, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(km), set.st));
+    HIPCHK(jit_launch(kjk.scan_sites, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(kms), set.st));
     return CRBM_OK;
   };
   int64_t total = 0;
@@ -2899,22 +2616,22 @@ int mutagenesis_any(crbm_handle* h, const RowSource& src, float* dfe, float* pll
   if (rc) return rc;
   const int n = src.n, L = src.L, A = h->A, K = h->K, LW = lw(h, L);
   int waves = 0;
-  if (!h->big && h->ms.POOL == 1 && env_int("CRBM_MUT_FUSED", 1) != 0)
+  if (!h->big() && h->ms().POOL == 1 && env_int("CRBM_MUT_FUSED", 1) != 0)
     for (waves = 4; waves >= 1; waves >>= 1)
-      if ((size_t)tab_bytes(h) + (size_t)waves * 3 * mut_plane(L) * sizeof(float) <= 160u * 1024u) break;
+      if ((size_t)tab_bytes(h->ms()) + (size_t)waves * 3 * mut_plane(L) * sizeof(float) <= 160u * 1024u) break;
   const bool fused = waves >= 1;
-  const unsigned lds = fused ? (unsigned)(tab_bytes(h) + waves * 3 * mut_plane(L) * (int)sizeof(float)) : 0u;
+  const unsigned lds = fused ? (unsigned)(tab_bytes(h->ms()) + waves * 3 * mut_plane(L) * (int)sizeof(float)) : 0u;
   h->mut_route = fused ? 1 : 2;
   rc = sweep_begin(h);
   if (rc) return rc;
   const size_t per = (size_t)mut_rows_per_seq(A, L);
-  const bool slabbed_fe = !fused && h->big && slab_fe_on(h);
+  const bool slabbed_fe = !fused && h->big() && slab_fe_on(h);
   // bytes per row: the outputs; on the general path also the row's expanded rows, their free energies (per sequence
   // and per motif) and, where the free energies run slab by slab, that pass's scratch (slab_launch_fe)
   size_t row_bytes = (dfe ? (size_t)L * A * sizeof(float) : 0) + sizeof(float);
   if (!fused) {
     row_bytes += per * ((size_t)LW * sizeof(uint32_t) + ((size_t)K + 1) * sizeof(float));
-    if (slabbed_fe) row_bytes += per * (size_t)h->slab->K * h->slab_n * sizeof(float);
+    if (slabbed_fe) row_bytes += per * (size_t)h->slab.K * h->slab_n * sizeof(float);
   }
   int slab = sweep_slab(src, row_bytes);
   if (!fused) slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)slab, ((size_t)1 << 30) / per));   // expanded rows are counted in int
@@ -2928,7 +2645,7 @@ int mutagenesis_any(crbm_handle* h, const RowSource& src, float* dfe, float* pll
       HIPCHK(set.own->mut_rows.ensure((size_t)slab * per * LW));
       HIPCHK(set.oa->ensure((size_t)slab * per));
       HIPCHK(set.ob->ensure((size_t)slab * per * K));
-      if (slabbed_fe) HIPCHK(set.fe_scratch->ensure((size_t)slab * per * h->slab->K * h->slab_n));
+      if (slabbed_fe) HIPCHK(set.fe_scratch->ensure((size_t)slab * per * h->slab.K * h->slab_n));
     }
   }
   return sweep_run(h, src, slab, 2,
@@ -3163,9 +2880,9 @@ int crbm_mutagenesis_resident(crbm_handle* h, int32_t start, int32_t end, float*
 int crbm_ais(crbm_handle* h, int32_t L, int32_t runs, uint32_t run_offset, const float* betas, int32_t nbetas,
              int32_t t0, int32_t t1, const float* base_c, uint64_t seed, uint8_t* state, float* logw) {
   ENTER();
-  ARGCHK(h->ms.POOL == 1, "crbm_ais: pooling > 1 is not supported (the pooled sampler and the pooled free energy normalise differently)");
+  ARGCHK(h->ms().POOL == 1, "crbm_ais: pooling > 1 is not supported (the pooled sampler and the pooled free energy normalise differently)");
   ARGCHK(h->A == 4, "crbm_ais: alphabets other than DNA's (input_dims != 4) are not supported");
-  ARGCHK(!h->big, "crbm_ais: models on the generic kernels are not supported");
+  ARGCHK(!h->big(), "crbm_ais: models on the generic kernels are not supported");
   ARGCHK(betas && logw, "null argument");
   ARGCHK(L >= h->M, "sequence length must be >= motif_length");
   ARGCHK((long)L * 4 < (1 << 20), "sequence too long");
@@ -3180,9 +2897,9 @@ int crbm_ais(crbm_handle* h, int32_t L, int32_t runs, uint32_t run_offset, const
   ARGCHK(t0 == 0 || state, "t0 > 0 needs the state of the runs");
   if (base_c)
     for (int a = 0; a < 4; ++a) ARGCHK(std::isfinite(base_c[a]), "base_c must be finite");
-  const AisLayout al = ais_layout(h->ms, L);
+  const AisLayout al = ais_layout(h->ms(), L);
   int waves = 4;
-  while (waves >= 1 && ais_lds_bytes(h->ms, al, waves) > 160L * 1024L) waves >>= 1;
+  while (waves >= 1 && ais_lds_bytes(h->ms(), al, waves) > 160L * 1024L) waves >>= 1;
   ARGCHK(waves >= 1, "crbm_ais: a run of this length does not fit the LDS beside the model's tables");
   const size_t nstate = (size_t)runs * L;
   if (t0 > 0)
@@ -3209,7 +2926,7 @@ int crbm_ais(crbm_handle* h, int32_t L, int32_t runs, uint32_t run_offset, const
   a.rng.seed_lo = (uint32_t)(seed & 0xffffffffu); a.rng.seed_hi = (uint32_t)(seed >> 32);
   a.rng.step = 0; a.rng.seq_offset = run_offset;
   const unsigned gx = (unsigned)std::max(1, std::min((runs + waves - 1) / waves, h->num_cu * 8));
-  const unsigned lds = (unsigned)ais_lds_bytes(h->ms, al, waves);
+  const unsigned lds = (unsigned)ais_lds_bytes(h->ms(), al, waves);
   for (int t = t0; t < t1; t += max_steps) {
     a.t0 = t; a.t1 = std::min(t1, t + max_steps);
     HIPCHK(jit_launch(h->jk.ais, a, gx, 1, 64u * (unsigned)waves, lds, h->stream));
@@ -3337,7 +3054,7 @@ int crbm_ipc_attach(crbm_handle* h, const uint8_t* handles, int32_t nranks, int3
   ENTER();
   ARGCHK(handles && nranks >= 1 && nranks <= IPC_MAX_RANKS && rank >= 0 && rank < nranks, "bad argument (at most 8 ranks: one node)");
   ARGCHK(!h->comm, "the handle already has an RCCL communicator");
-  ARGCHK(!h->big, "the mapped-buffer all-reduce serves models of the LDS-resident kernels; this one (generic kernels) takes RCCL");
+  ARGCHK(!h->big(), "the mapped-buffer all-reduce serves models of the LDS-resident kernels; this one (generic kernels) takes RCCL");
   int rc = ipc_allocate(h);
   if (rc) return rc;
   for (int r = 0; r < nranks; ++r) {
@@ -3435,7 +3152,7 @@ int crbm_time_allreduce(crbm_handle* h, int32_t launches, float* total_ms) {
 
 int crbm_get_launch_info(const crbm_handle* h, crbm_launch_info* out) {
   if (!h || !out) return CRBM_ERR_INVALID;
-  if (h->big) {          // generic kernels: no specialised geometry to report
+  if (h->big()) {          // generic kernels: no specialised geometry to report
     *out = crbm_launch_info();
     out->gibbs_sparse = 1; out->chain_parts = 1; out->gibbs_block = 256;
     out->activity_ppm = h->activity < 0.0 ? -1 : (int32_t)(h->activity * 1e6 + 0.5);
@@ -3443,18 +3160,15 @@ int crbm_get_launch_info(const crbm_handle* h, crbm_launch_info* out) {
     return CRBM_OK;
   }
   // the data-half statistics kernel at the chains' shape (stats_mfma_body)
-  const int tabs = h->ms.TAB * 4;
-  const StatsMfmaLayout st = stats_mfma_layout(h->ms, 1, h->Lf, 0, tabs);
+  const int tabs = h->ms().TAB * 4;
+  const StatsMfmaLayout st = stats_mfma_layout(h->ms(), 1, h->Lf, 0, tabs);
   const int lds = std::max(st.region_floats * 4 + tabs, st.combine_bytes);
-  out->nq = h->ms.NQ; out->group = h->GS;   // of the plain chain launch this structure describes
-  // the geometry of a plain chain launch (crbm_gibbs_steps*): the solo one where the model has it
-  const bool parts = h->variant == 1 && h->chain_parts > 1;
-  const bool solo = h->variant == 1 && h->solo_threads > 0;
-  out->chain_parts = parts ? h->chain_parts : 1;
-  out->gibbs_grid = parts ? h->part_grid : solo ? h->solo_grid : h->gibbs_grid;
-  out->gibbs_block = parts ? h->part_threads : solo ? h->solo_threads : h->gibbs_threads;
-  out->gibbs_seqs_per_tile = parts ? h->gl_part.S : solo ? h->gl_solo.S : h->gl.S;
-  out->gibbs_lds_bytes = parts ? h->gl_part.lds_bytes : solo ? h->gl_solo.lds_bytes : h->gl.lds_bytes;
+  // a plain chain launch (crbm_gibbs_steps*): its letter grouping, its geometry
+  const ChainGeom& g = plain_geom(h->plan, h->variant);
+  out->nq = h->ms().NQ; out->group = h->plan.GS;
+  out->chain_parts = h->variant == 1 ? h->plan.chain_parts : 1;
+  out->gibbs_grid = g.grid; out->gibbs_block = g.threads;
+  out->gibbs_seqs_per_tile = g.gl.S; out->gibbs_lds_bytes = g.gl.lds_bytes;
   out->stats_grid_x = h->stats_rows > 0 ? h->stats_rows
                                         : h->num_cu * std::max(1, std::min(2048 / st.threads, (160 * 1024) / std::max(1, lds)));
   out->stats_grid_y = 1;
@@ -3509,7 +3223,7 @@ int crbm_last_shader_clock(crbm_handle* h, float* mhz) {
 int64_t crbm_gibbs_state_bytes(const crbm_handle* h) {
   if (!h) return 0;
   const int64_t masks = (int64_t)h->B * h->Lf * h->NW * 4 * (1 + h->ds);
-  const int64_t vout = (int64_t)h->B * h->gl.LWs * 4;
+  const int64_t vout = (int64_t)h->B * h->LWs * 4;
   return 2 * masks + vout;   // masks read + written, last visible sample written
 }
 

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE shared by the sanitizer tests (tests/test_emu*.py, tests/test_sweep_host.py): builds a driver of
+"""TEST INFRASTRUCTURE shared by the sanitizer tests (tests/test_emu*.py, tests/test_sweep_host.py, tests/test_plan_host.py): builds a driver of
 this folder into a library with ASan + UBSan, gives the environment of the child process that loads it, runs one case
 of a test file in such a child, and holds what the children themselves share (ctypes pointers, a model's table image,
 the random model of a case).  A plain module: every test file imports it (as tests.emu.harness, with the repository

@@ -388,3 +388,63 @@ def test_time_gibbs_waits_for_the_tables_after_set_params():
     twin.motifs.set_value(W2)
     if assert_chain_steps(twin, o, 2) == 0:                 # no tie met: the oracle's chain is the handle's
         np.testing.assert_array_equal(ha[:32], o.fantasy_h)
+
+
+# ---- crbm_create takes the plan crbm_precompile compiled for (crbm_plan.h) -----------------------------------------------
+# (K, M, ds, batchsize, Lf) of models __graft_entry__.build() precompiles: plain, partitioned, slabbed generic; config #5
+# at 8192 chains for the recorded plan
+PLAN_SHAPES = [(10, 15, 0, 20, 200), (10, 15, 0, 8192, 186), (300, 10, 0, 20, 51)]
+PLAN_IDS = ["plain", "partitioned", "slabbed_generic"]
+
+
+def _create(K, M, ds, B, Lf):
+    """a bare handle of the model, configured as crbm_amd.csrc.build.precompile configures it"""
+    from crbm_amd import _lib
+    lib = _lib.load()
+    cfg = _lib.CrbmConfig(num_motifs=K, motif_length=M, input_dims=4, doublestranded=ds, batchsize=B, cd_k=1, pooling=1,
+                          fantasy_hidden_len=Lf, learning_rate=0.1, momentum=0.9, rho=0.01, lambda_rate=0.1, seed=0, device=0,
+                          reserved=0)
+    h = ctypes.c_void_p()
+    assert lib.crbm_create(ctypes.byref(cfg), ctypes.byref(h)) == 0, lib.crbm_last_error(None).decode()
+    return lib, h
+
+
+@pytest.mark.parametrize("shape", PLAN_SHAPES, ids=PLAN_IDS)
+def test_create_takes_the_precompiled_code_objects(shape):
+    """The JIT cache is keyed by what the launch plan chooses (letter groupings, occupancy hint, block bound, slab model):
+    a handle of a precompiled model must find its code object in the in-tree cache -- creating it adds no file there."""
+    import os
+    from crbm_amd import _lib
+    for knob in ("CRBM_JIT_CACHE", "CRBM_JIT_DEFINES", "CRBM_JIT_NOCACHE"):
+        if os.environ.get(knob):
+            pytest.skip(knob + " is set: handles do not take the in-tree cache as the build left it")
+    cache = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc", "jit_cache")
+    before = sorted(os.listdir(cache))
+    assert before, "the build leaves the precompiled code objects in " + cache
+    lib, h = _create(*shape)
+    lib.crbm_destroy(h)
+    assert sorted(os.listdir(cache)) == before
+
+
+@pytest.mark.parametrize("shape", PLAN_SHAPES + [(20, 15, 1, 8192, 486)], ids=PLAN_IDS + ["partitioned_cfg5"])
+def test_launch_info_is_the_recorded_plan(shape):
+    """crbm_get_launch_info of a handle against tests/golden/launch_plans.json (recorded before crbm_plan.h existed)"""
+    import json
+    import os
+    import torch
+    from crbm_amd import _lib
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_plans.json")) as f:
+        golden = json.load(f)
+    num_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    if num_cu != golden["num_cu"]:
+        pytest.skip("recorded on a device of %d compute units, this one has %d" % (golden["num_cu"], num_cu))
+    K, M, ds, B, Lf = shape
+    rows = [r["info"] for r in golden["plans"]["default"]
+            if (r["config"]["num_motifs"], r["config"]["motif_length"], r["config"]["doublestranded"],
+                r["config"].get("batchsize", 20), r["config"].get("fantasy_hidden_len", 200), r["config"].get("pooling", 1)) == (K, M, ds, B, Lf, 1)]
+    assert len(rows) == 1
+    lib, h = _create(*shape)
+    info = _lib.CrbmLaunchInfo()
+    assert lib.crbm_get_launch_info(h, ctypes.byref(info)) == 0
+    lib.crbm_destroy(h)
+    assert {f: getattr(info, f) for f in golden["fields"]} == rows[0]
