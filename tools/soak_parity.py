@@ -1,6 +1,7 @@
 """Randomised parity soak: random model shapes / batch shapes, one PCD-k training step and a
 few Gibbs steps against the float64 oracle.  usage: python tools/soak_parity.py [n_cases] [seed]
-(test infrastructure: imports the oracle)"""
+(test infrastructure: imports the oracle)
+The launch structures it draws at random (CRBM_STATS unset / two / split) are pinned, raw sums against the oracle, in tests/test_gpu_statistics.py."""
 import os
 import sys
 import time
