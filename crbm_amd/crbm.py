@@ -524,6 +524,23 @@ class CRBM(object):
             raw = call(count.value)          # more sites than the first buffer took: the scan is computed again
         return raw[:count.value]
 
+    def _scan_cuts(self, stream, offsets):
+        """[lo, hi) of the pieces of at most _SCAN_MAX letters a stream is scanned in, cut at record boundaries"""
+        lo = 0
+        while True:
+            hi = stream.size
+            if hi - lo > self._SCAN_MAX:
+                if offsets is None:
+                    raise ValueError("a stream of more than 2^31 - 1 letters needs offsets (it is cut at record boundaries)")
+                i = int(np.searchsorted(offsets, lo + self._SCAN_MAX + 1, side="right")) - 1
+                hi = int(offsets[i]) - 1     # the separator in front of record i: the piece ends with the record before
+                if hi <= lo:
+                    raise ValueError("a record of more than 2^31 - 1 letters cannot be scanned")
+            yield lo, hi
+            if hi >= stream.size:
+                break
+            lo = hi + 1
+
     def scanSites(self, stream, threshold=0.5, offsets=None):
         """motifSites for whole records of any length: `stream` is a 1-D uint8 array of codes, 0..3 = A,C,G,T and
         4 = no letter (N, ambiguity codes, record separators) -- sequences.seqsToStream / fastaToStream make it.  Every
@@ -534,21 +551,7 @@ class CRBM(object):
         "x.bed", names=names) writes them as BED.  Models with pooling, other alphabets or motifs beyond 64 letters are
         refused."""
         t, stream, offsets = self._scan_input(stream, threshold, offsets)
-        pieces, lo = [], 0
-        while True:                          # pieces of at most _SCAN_MAX letters, cut at record boundaries
-            hi = stream.size
-            if hi - lo > self._SCAN_MAX:
-                if offsets is None:
-                    raise ValueError("a stream of more than 2^31 - 1 letters needs offsets (it is cut at record boundaries)")
-                i = int(np.searchsorted(offsets, lo + self._SCAN_MAX + 1, side="right")) - 1
-                hi = int(offsets[i]) - 1     # the separator in front of record i: the piece ends with the record before
-                if hi <= lo:
-                    raise ValueError("a record of more than 2^31 - 1 letters cannot be scanned")
-            raw = self._scan_call(stream[lo:hi], t)
-            pieces.append((lo, raw))
-            if hi >= stream.size:
-                break
-            lo = hi + 1
+        pieces = [(lo, self._scan_call(stream[lo:hi], t)) for lo, hi in self._scan_cuts(stream, offsets)]
         n = sum(r.size for _, r in pieces)
         out = np.empty(n, dtype=self.SITE_DTYPE)
         pos = np.empty(n, dtype=np.int64)
@@ -567,6 +570,41 @@ class CRBM(object):
             out["seq"] = seq
             out["start"] = pos - offsets[seq]
         return out
+
+    def _hist_call(self, stream, lo, hi, bins):
+        """crbm_scan_histogram_codes over one piece of at most _SCAN_MAX letters: (counts (K, S, bins) uint64, windows)"""
+        S = 2 if self.doublestranded else 1
+        counts = np.zeros((self.num_motifs, S, bins), dtype=np.uint64)
+        windows = ctypes.c_int64(0)
+        self._call("crbm_scan_histogram_codes", stream.ctypes.data_as(_lib._U8P), stream.size, lo, hi, bins,
+                   counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(windows))
+        return counts, windows.value
+
+    def scoreHistogram(self, stream, bins=512, lo=-16.0, hi=16.0, offsets=None):
+        """The scores scanSites would see on `stream`, as a calibrate.ScoreHistogram: per motif and strand the counts of
+        the log-odds x (prob = sigmoid(x)) of every valid window in `bins` equal bins over [lo, hi), the first and the
+        last bin open to the outside.  Run it on a background -- sequences.shuffleStream(stream, seed) of the data --
+        and take per-motif thresholds (thresholds(fpr)) or p-values of scanSites records (pvalues(sites)) from the
+        result.  Nothing but the counts leaves the device.  `stream` and `offsets` as in scanSites; lo and hi are
+        rounded to float32.  The same models are refused, and more than 1024 bins."""
+        _, stream, offsets = self._scan_input(stream, 0.0, offsets)
+        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= 1024:
+            raise ValueError("bins must be an integer in [1, 1024]")
+        try:
+            with np.errstate(over="ignore"):
+                lo, hi = float(np.float32(lo)), float(np.float32(hi))
+        except (TypeError, ValueError):
+            raise ValueError("lo and hi must be numbers")
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError("lo and hi must be finite with lo < hi")
+        from .calibrate import ScoreHistogram
+        S = 2 if self.doublestranded else 1
+        counts, windows = np.zeros((self.num_motifs, S, int(bins)), np.int64), 0
+        for a, b in self._scan_cuts(stream, offsets):
+            c, w = self._hist_call(stream[a:b], lo, hi, int(bins))
+            counts += c.astype(np.int64)
+            windows += w
+        return ScoreHistogram(counts, np.linspace(lo, hi, int(bins) + 1), windows, self.doublestranded)
 
     def motifBestSites(self, data):
         """The best site of every (sequence, motif): dict of 'start' (n,K) int32, 'strand' (n,K) int8 and

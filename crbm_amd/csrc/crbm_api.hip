@@ -178,6 +178,7 @@ struct crbm_handle {
   // annealed importance sampling (crbm_ais): the ladder, cA, the runs' log weights and letter codes between launches
   DevBuf<float> ais_betas, ais_base, ais_logw;
   DevBuf<uint8_t> ais_state;
+  DevBuf<unsigned long long> hist;                 // score histogram (crbm_scan_histogram_codes): [K][S][nbins], then the valid windows; both streams add into it
   float* d_sums = nullptr;
   int dataset_n[CRBM_DATASET_SLOTS] = {0, 0}, dataset_L[CRBM_DATASET_SLOTS] = {0, 0};
   int slot = 0;
@@ -1628,7 +1629,7 @@ int crbm_destroy(crbm_handle* h) {
     b.scan_valid.release(); b.scan_off.release(); b.scan_lanes.release(); b.scan_tiles.release();
     b.mut_df.release(); b.mut_pll.release(); b.mut_rows.release();
   }
-  h->ais_betas.release(); h->ais_base.release(); h->ais_logw.release(); h->ais_state.release();
+  h->ais_betas.release(); h->ais_base.release(); h->ais_logw.release(); h->ais_state.release(); h->hist.release();
   if (h->jk.module) (void)hipModuleUnload(h->jk.module);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -2602,6 +2603,129 @@ int scan_sites_any(crbm_handle* h, const uint8_t* codes, int64_t T, float thresh
   return CRBM_OK;
 }
 
+// ---- score histogram (crbm_scan_histogram_codes) --------------------------------------------------------------------
+// scan_sites_any's sweep -- the same segments, halo, sets and slab budget -- with crbm_scan_hist in place of the two
+// passes: bytes up, scan_encode_kernel, one launch that adds the segment's scores into h->hist.  The histogram is
+// zeroed on the main stream, which is then waited for, before the first segment; both streams add into it with
+// integer atomics; it is copied back once, after both streams are idle.  A segment has nothing to collect.
+// CRBM_HIST_VARIANT picks how a wave spreads its LDS adds (scan_hist_body: 0 in order, 1 lane-rotated motif order,
+// 2 counter sets per wave); CRBM_HIST_TIMING=1 (tools/bench_calibrate.py) puts events around every segment's kernels
+// and their sum on stderr.
+int scan_hist_any(crbm_handle* h, const uint8_t* codes, int64_t T, float lo, float hi, int32_t nbins, uint64_t* counts,
+                  int64_t* windows) {
+  ARGCHK(counts, "null argument");
+  ARGCHK(nbins >= 1 && nbins <= 1024, "nbins must lie in [1, 1024]");
+  ARGCHK(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "lo and hi must be finite with lo < hi");
+  ARGCHK(T >= 0 && T <= (int64_t)INT32_MAX, "stream length must lie in [0, 2^31 - 1]");
+  ARGCHK(codes || T == 0, "null argument");
+  ARGCHK(h->A == 4, "crbm_scan_histogram_codes: the alphabet must be DNA's (input_dims == 4)");
+  ARGCHK(h->ms().POOL == 1, "crbm_scan_histogram_codes: pooling > 1 is not supported (pool groups have no anchor in a stream)");
+  const ModelShape& kms = h->big() ? h->slab.ms : h->ms();
+  const JitKernels& kjk = h->big() ? h->slab.jk : h->jk;
+  ARGCHK((!h->big() || h->slab.K) && tab_bytes(kms) <= 160 * 1024, "crbm_scan_histogram_codes: models that run on the generic kernels alone (motifs beyond 64 letters) are not supported");
+  const int M = h->M, S = h->ds ? 2 : 1;
+  const int variant = env_int("CRBM_HIST_VARIANT", 1);
+  const HistPlan hp = hist_plan(tab_bytes(kms), kms.NQ, S, nbins, variant == 2 ? 8 : 1);
+  ARGCHK(hp.gq >= 1, "crbm_scan_histogram_codes: the counters of four motifs do not fit beside the model's gather table (fewer bins)");
+  const float inv_w = (float)nbins / (hi - lo);
+  ARGCHK(std::isfinite(inv_w) && inv_w > 0.f, "hi - lo is too small or too large for nbins");
+  const size_t cells = (size_t)h->K * S * nbins;
+  if (T < M) {
+    std::memset(counts, 0, cells * sizeof(uint64_t));
+    if (windows) *windows = 0;
+    return CRBM_OK;
+  }
+  const int starts_all = (int)(T - M + 1), nslab = h->big() ? h->slab_n : 1;
+  int rc = sweep_begin(h);
+  if (rc) return rc;
+  const size_t per_start = 4 + (size_t)4 * nslab;          // scan_sites_any's figure: the same segments for the same budget
+  int seg = slab_rows(starts_all, per_start);
+  if (!getenv("CRBM_SLAB_BYTES")) seg = (int)std::min<size_t>((size_t)seg, std::max<size_t>(1, (32u << 20) / per_start));
+  const ScanLayout lay = scan_layout((long)seg + M - 1, seg);
+  const int nsets = seg < starts_all ? 2 : 1;
+  for (int i = 0; i < nsets; ++i) {
+    const SweepSet set = sweep_set(h, i);
+    HIPCHK(set.stage->ensure(((size_t)seg + M - 1 + 3) / 4));
+    HIPCHK(set.letters->ensure((size_t)lay.letter_words));
+    HIPCHK(set.own->scan_valid.ensure((size_t)lay.valid_words));
+  }
+  HIPCHK(h->hist.ensure(cells + 1));
+  HIPCHK(hipMemsetAsync(h->hist.p, 0, (cells + 1) * sizeof(unsigned long long), h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));                 // zero before either stream adds
+  const bool timing = env_int("CRBM_HIST_TIMING", 0) != 0;
+  struct Events {                                          // destroyed on every way out
+    hipEvent_t e[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    ~Events() {
+      for (auto& set : e)
+        for (hipEvent_t ev : set)
+          if (ev) (void)hipEventDestroy(ev);
+    }
+  } events;
+  auto& tev = events.e;
+  double device_ms = 0.0;
+  int segments = 0;
+  if (timing)
+    for (int i = 0; i < 2; ++i)
+      for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
+  rc = run_slabs(starts_all, seg, 2,
+    [&](int, int si, int start, int cnt) -> int {
+      const SweepSet set = sweep_set(h, si);
+      const long n = (long)cnt + M - 1;
+      const ScanLayout l = scan_layout(n, cnt);
+      HIPCHK(hipMemcpyAsync(set.stage->p, codes + start, (size_t)n, hipMemcpyHostToDevice, set.st));
+      if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
+      ScanEncodeArgs e;
+      e.codes = reinterpret_cast<const unsigned char*>(set.stage->p);
+      e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;
+      e.n = n; e.valid_words = l.valid_words;
+      hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
+      HIPCHK(hipGetLastError());
+      ScanHistArgs a;
+      a.tables = h->big() ? h->d_slab_tables : h->d_tables;
+      a.letters = set.letters->p; a.valid = set.own->scan_valid.p; a.hist = h->hist.p;
+      a.starts = cnt; a.tiles = l.tiles; a.nbins = nbins; a.gq = hp.gq; a.copies = hp.copies; a.rotate = variant == 1;
+      a.lo = lo; a.inv_w = inv_w; a.table_stride = kms.TABLES_ALL;
+      if (h->big()) a.plan = slab_plan(h);
+      else { a.plan.Ks = h->K; a.plan.K = h->K; a.plan.last_k0 = 0; }
+      // eight waves a block; as many blocks as the CUs hold at this LDS footprint, each with at least two tiles a wave
+      const int per_cu = (int)std::max<long>(1, std::min<long>(4, 160L * 1024 / hp.lds));
+      const unsigned gx = (unsigned)std::max(1, std::min((a.tiles + 15) / 16, std::max(1, h->num_cu * per_cu / nslab)));
+      HIPCHK(jit_launch(kjk.scan_hist, a, gx, (unsigned)nslab, 512, (unsigned)hp.lds, set.st));
+      if (timing) HIPCHK(hipEventRecord(tev[si][1], set.st));
+      return CRBM_OK;
+    },
+    [&](int, int si, int, int) -> int {
+      const SweepSet set = sweep_set(h, si);
+      HIPCHK(hipStreamSynchronize(set.st));               // the set's buffers are free again
+      if (timing) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, tev[si][0], tev[si][1]));
+        device_ms += ms;
+        ++segments;
+      }
+      return CRBM_OK;
+    },
+    [&] { sweep_drain(h); });
+  if (timing && !rc) fprintf(stderr, "crbm_scan_histogram_codes: kernels %.3f ms over %d segments\n", device_ms, segments);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream2));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  uint32_t flags = 0;
+  HIPCHK(hipMemcpyAsync(&flags, h->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (flags) {
+    HIPCHK(hipMemsetAsync(h->d_flags, 0, sizeof(uint32_t), h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return fail(h, CRBM_ERR_INVALID, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
+  }
+  std::vector<unsigned long long> out(cells + 1);
+  HIPCHK(hipMemcpyAsync(out.data(), h->hist.p, (cells + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (size_t i = 0; i < cells; ++i) counts[i] = (uint64_t)out[i];
+  if (windows) *windows = (int64_t)out[cells];
+  return CRBM_OK;
+}
+
 // ---- in-silico mutagenesis (crbm_mutagenesis*) ----------------------------------------------------------------------
 // dF (n,L,A) and / or pll (n) over a source, a two-stream sweep.  Specialised models without pooling: the fused
 // crbm_mutagenesis pass (mutagenesis_body; as many waves per block as the LDS holds accumulators beside the tables).
@@ -2850,6 +2974,12 @@ int crbm_scan_sites_codes(crbm_handle* h, const uint8_t* codes, int64_t T, float
                           crbm_site* sites, int64_t* count) {
   ENTER();
   return scan_sites_any(h, codes, T, threshold, capacity, sites, count);
+}
+
+int crbm_scan_histogram_codes(crbm_handle* h, const uint8_t* codes, int64_t T, float lo, float hi, int32_t nbins,
+                              uint64_t* counts, int64_t* windows) {
+  ENTER();
+  return scan_hist_any(h, codes, T, lo, hi, nbins, counts, windows);
 }
 
 int crbm_mutagenesis(crbm_handle* h, const float* v, int32_t n, int32_t L, float* dfe, float* pll) {

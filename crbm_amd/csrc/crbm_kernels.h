@@ -3050,6 +3050,136 @@ __device__ void scan_sites_body(const ScanArgs& a) {
   }
 }
 
+// ===========================================================================
+// Score histogram (crbm_scan_histogram_codes): the stream scan with a histogram per (motif, strand) in place of records.
+// Same input, tiles and slabs as scan_sites_body; the score of a valid window is the log-odds x = x_of_z(z) of the z
+// the scan's gather returns (the same calls in the same order; single-stranded models: z summed over both
+// orientations, one strand), so that sigmoid(x) is the probability the scan reports.
+// THE BIN RULE: t = (x - lo) * inv_w with inv_w = nbins / (hi - lo) formed on the host in fp32; the bin is 0 for
+// t < 0, nbins - 1 for t >= nbins, (int)t otherwise -- the first bin holds everything below lo, the last everything at
+// or above hi.  (A NaN score, which finite parameters cannot produce, would land in bin 0.)
+// Counts go into 32-bit LDS counters behind the gather table -- a block sees fewer than 2^31 starts per segment -- for
+// `gq` motif quads at a time: groups of quads in the outer loop, tiles in the inner one, the non-zero counters of a
+// group added to hist [K][S][nbins] with 64-bit integer atomics before the next group starts.  Integer adds only: the
+// same bits for every geometry, segment size and run.  hist[K * S * nbins] receives the number of valid windows,
+// counted by slab 0 on its first group.
+// The 64 lanes of a wave score the same motif at the same moment, and background scores cluster in few bins:
+//   variant 0  every lane walks the motifs of a gather in order, one counter set per block;
+//   variant 1  lane l starts at motif l mod NV (a select tree over the NV counter addresses per step);
+//   variant 2  as 0 with `copies` counter sets, wave w adds into set w mod copies.
+// ===========================================================================
+struct ScanHistArgs {
+  const float* tables;                 // the first slab's image
+  const uint32_t* letters;
+  const unsigned long long* valid;
+  unsigned long long* hist;            // [K][S][nbins], then the valid windows
+  int32_t starts, tiles;               // window starts of the segment, tiles of 64 of them
+  int32_t nbins;
+  int32_t gq;                          // motif quads whose counters the LDS holds: a multiple of the gather's quads, or fewer
+  int32_t copies;                      // counter sets (variant 2; else 1)
+  int32_t rotate;                      // variant 1
+  float lo, inv_w;
+  int32_t table_stride;                // floats
+  SlabPlan plan;
+};
+// v[j] for a lane-dependent j in [0, N): a tree of selects, no indexed register access
+template <int N>
+__device__ __forceinline__ int select_entry(const int (&v)[N], int j) {
+  constexpr int P2 = N <= 4 ? 4 : N <= 8 ? 8 : 16;
+  static_assert(N <= 16, "a gather holds at most 16 motifs");
+  int t[P2];
+#pragma unroll
+  for (int i = 0; i < P2; ++i) t[i] = i < N ? v[i] : -1;
+#pragma unroll
+  for (int bit = 0; (1 << bit) < P2; ++bit) {
+    const bool odd = (j >> bit) & 1;
+#pragma unroll
+    for (int m = 0; m < (P2 >> (bit + 1)); ++m) t[m] = odd ? t[2 * m + 1] : t[2 * m];
+  }
+  return t[0];
+}
+
+template <class C>
+__device__ void scan_hist_body(const ScanHistArgs& a) {
+  if constexpr (C::POOL == 1) {       // refused on the host, as the scan
+    constexpr int M = C::M, S = C::DS ? 2 : 1;
+    constexpr int NQW = C::NQ < 4 ? C::NQ : 4, NV = 4 * NQW;
+    constexpr bool BOTH = !C::DS;
+    HIP_DYNAMIC_SHARED(float, smem);
+    float* Tf = smem;
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + C::TAB);    // [copies][4 gq][S][nbins], then the block's valid windows
+    const int y = (int)blockIdx.y, k0 = slab_k0(a.plan, y);
+    const int kskip = y > 0 ? max(0, slab_k0(a.plan, y - 1) + a.plan.Ks - k0) : 0;   // motifs the neighbouring slab counts
+    const int kend = min(C::K, a.plan.K - k0);
+    const int nb = a.nbins, row = S * nb, per = 4 * a.gq * row;    // counters of a motif, of a counter set
+    uint32_t* wcnt = cnt + (size_t)a.copies * per;
+    copy_tables<C::TAB>(Tf, a.tables + (size_t)y * a.table_stride + C::OFF_TF);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    uint32_t* mine = cnt + (size_t)(wave % a.copies) * per;
+    const float lo = a.lo, inv_w = a.inv_w, nbf = (float)nb;
+    const int r0 = lane % NV;
+    for (int g0 = 0; g0 < C::NQ; g0 += a.gq) {
+      const int g1 = min(g0 + a.gq, C::NQ);
+      for (int i = threadIdx.x; i < a.copies * per + (g0 == 0 ? 1 : 0); i += blockDim.x) cnt[i] = 0u;
+      __syncthreads();                 // (the first one also stands behind copy_tables)
+      for (int t = blockIdx.x * nwaves + wave; t < a.tiles; t += gridDim.x * nwaves) {
+        const int s = 64 * t + lane;
+        bool ok = s < a.starts;
+        if (ok) {                      // all M validity bits from s on, as scan_sites_body
+          const int sh = s & 63;
+          const unsigned long long v0 = a.valid[s >> 6], v1 = a.valid[(s >> 6) + 1];
+          const unsigned long long v = sh ? (v0 >> sh) | (v1 << (64 - sh)) : v0;
+          const unsigned long long need = M < 64 ? (1ull << M) - 1ull : ~0ull;
+          ok = (v & need) == need;
+        }
+        if (g0 == 0 && y == 0) {       // wave-uniform
+          const unsigned long long m = __ballot(ok);
+          if (lane == 0 && m) atomicAdd(wcnt, (uint32_t)__popcll(m));
+        }
+        if (!ok) continue;
+        const LetterWin<M> w = letter_window<M>(a.letters, s);
+#pragma unroll 1
+        for (int q0 = (g0 / NQW) * NQW; q0 < g1; q0 += NQW)
+#pragma unroll 1
+          for (int strand = 0; strand < S; ++strand) {
+            float z[NV];
+            conv_gather_quads<C, NQW>(Tf, strand ? revcomp_window<M>(w) : w, q0, z);
+            if (BOTH) conv_gather_quads<C, NQW, true>(Tf, revcomp_window<M>(w), q0, z);
+            int at[NV];                // the counter of motif 4 q0 + j, -1: not this block's, or not resident
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+              const int kk = 4 * q0 + j, qq = q0 + j / 4;
+              const float tb = (x_of_z(z[j]) - lo) * inv_w;
+              const int bin = !(tb >= 0.f) ? 0 : tb >= nbf ? nb - 1 : (int)tb;
+              const bool live = kk >= kskip && kk < kend && qq >= g0 && qq < g1;
+              at[j] = live ? ((kk - 4 * g0) * S + strand) * nb + bin : -1;
+            }
+            if (a.rotate) {
+#pragma unroll
+              for (int i = 0; i < NV; ++i) {
+                const int jj = i + r0 < NV ? i + r0 : i + r0 - NV;
+                const int ad = select_entry<NV>(at, jj);
+                if (ad >= 0) atomicAdd(mine + ad, 1u);
+              }
+            } else {
+#pragma unroll
+              for (int j = 0; j < NV; ++j)
+                if (at[j] >= 0) atomicAdd(mine + at[j], 1u);
+            }
+          }
+      }
+      __syncthreads();
+      for (int i = threadIdx.x; i < per; i += blockDim.x) {
+        uint32_t c = 0;
+        for (int set = 0; set < a.copies; ++set) c += cnt[(size_t)set * per + i];
+        if (c) atomicAdd(a.hist + (size_t)(k0 + 4 * g0) * row + i, (unsigned long long)c);   // (counters of motifs past kend stay 0)
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0 && y == 0 && *wcnt) atomicAdd(a.hist + (size_t)a.plan.K * row, (unsigned long long)*wcnt);
+  }
+}
+
 #ifdef CRBM_DEFINE_MISC_KERNELS
 // ===========================================================================
 // Model-independent kernels, compiled ahead of time into libcrbm_hip.so.

@@ -59,6 +59,31 @@ inline ScanLayout scan_layout(long n, long starts) {
   s.tiles = (int)((starts + 63) / 64);
   return s;
 }
+// Score histogram (crbm_kernels.h, scan_hist_body): the 32-bit counters of `gq` motif quads, [4 gq][S][nbins], `copies`
+// times, and one word for the valid windows stand behind the gather table (tab_bytes) in at most 160 KB of LDS.  gq is
+// all NQ quads when they fit, else the largest multiple of the gather's four quads that does, else what fits (the
+// kernel then repeats a gather per group); 0: not even one quad fits.  Counter sets beyond the first (want_copies > 1)
+// are granted only while they cost no extra group.
+struct HistPlan {
+  int gq, copies;
+  long lds;                         // bytes of dynamic LDS
+};
+inline HistPlan hist_plan(int tab_bytes, int NQ, int S, int nbins, int want_copies) {
+  const long quad = 16L * S * nbins, room = 160L * 1024 - tab_bytes - 4;
+  auto fit = [&](int copies) {
+    long gq = room / (quad * copies);
+    if (gq >= NQ) gq = NQ;
+    else if (gq >= 4) gq -= gq % 4;
+    return (int)(gq < 0 ? 0 : gq);
+  };
+  HistPlan p;
+  p.gq = fit(1);
+  p.copies = 1;
+  for (int c = want_copies; c > 1; --c)
+    if (fit(c) == p.gq) { p.copies = c; break; }
+  p.lds = tab_bytes + quad * p.gq * p.copies + 4;
+  return p;
+}
 // Largest motif length the letter windows hold (two 64-bit words); the number of motifs is
 // bounded by what the LDS holds (tables + one chain: choose_gibbs_geometry refuses beyond)
 // and by the statistics kernel (one role of 64 threads per 16 motifs, at most 1024 threads per block).

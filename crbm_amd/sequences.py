@@ -198,6 +198,23 @@ def fastaToStream(filename):
     return seqsToStream(seqs, ids)
 
 
+def shuffleStream(stream, seed):
+    """The background of a stream for CRBM.scoreHistogram: the letters of every maximal run of letters (codes 0..3)
+    permuted uniformly at random, every code 4 -- gaps and record separators -- where it was.  Each run, and with it
+    each record, keeps its length and composition; dinucleotide frequencies are not preserved.  The same seed gives
+    the same stream."""
+    if not isinstance(stream, np.ndarray) or stream.dtype != np.uint8 or stream.ndim != 1:
+        raise ValueError("stream must be a one-dimensional uint8 array of codes 0..4 (seqsToStream)")
+    out = stream.copy()
+    letter = stream < STREAM_GAP
+    pos = np.flatnonzero(letter)
+    if pos.size:
+        run = np.cumsum(~letter)[pos]                        # the letters of a run have the same number of gaps before them
+        order = np.lexsort((np.random.default_rng(seed).random(pos.size), run))
+        out[pos] = stream[pos[order]]
+    return out
+
+
 def load_sample(filename=None):
     """One-hot sample data (sequences.py:120-134).  The reference ships an Oct4
     ChIP-seq FASTA inside its package; this package carries no data files, so

@@ -243,6 +243,25 @@ int crbm_motif_sites_resident(crbm_handle* h, int32_t start, int32_t end, float 
 int crbm_scan_sites_codes(crbm_handle* h, const uint8_t* codes, int64_t T, float threshold, int64_t capacity,
                           crbm_site* sites, int64_t* count);
 
+/* ---- score histogram: what the scan's scores look like on a background -----------
+ * The stream scan with a histogram per (motif, strand) in place of records: which threshold gives which rate of sites,
+ * and how surprising a site is.  Stream, windows and validity as crbm_scan_sites_codes.  The score of a valid window,
+ * motif k and strand s is the log-odds x with prob = sigmoid(x), prob the probability the scan reports (x keeps
+ * resolution where prob saturates); s = 0 is the + strand (the only one of a single-stranded model, S = 1), s = 1
+ * the - strand of a double-stranded one (S = 2).
+ * The bin rule: t = (x - lo) * inv_w with inv_w = nbins / (hi - lo) in fp32; the bin is 0 for t < 0, nbins - 1 for
+ * t >= nbins, (int)t otherwise.  The first bin therefore holds everything below lo, the last everything at or above hi.
+ * counts [K][S][nbins] is overwritten; *windows (may be NULL) is the number of valid windows.  For every (k, s),
+ * sum_b counts[k][s][b] == *windows exactly.  Integer adds only: the same bits in every run, for every launch geometry
+ * and every CRBM_SLAB_BYTES.  A stream shorter than M, or without a valid window, gives all zeros and no error.
+ * Served: the models crbm_scan_sites_codes serves, when at least four motifs' counters (16 S nbins bytes) fit beside
+ * the model's gather table in 160 KB of LDS.
+ * CRBM_ERR_INVALID: what the scan refuses (pooling > 1, another alphabet, a generic-only model, a code above 4, T < 0,
+ * T > 2^31 - 1); nbins < 1 or > 1024; lo or hi not finite, or lo >= hi; counts == NULL.  The handle stays usable
+ * after a refusal; counts is then left as it was. */
+int crbm_scan_histogram_codes(crbm_handle* h, const uint8_t* codes, int64_t T, float lo, float hi, int32_t nbins,
+                              uint64_t* counts, int64_t* windows);
+
 /* ---- in-silico mutagenesis and pseudo-log-likelihood -----------------------------
  * WHICH bases matter.  With F(v) = L * crbm_free_energy(v), the unnormalised free energy of one sequence (derived from
  * theano_freeEnergyForData, convRBM.py:657-676: the hidden terms of all motifs and strands, pooled form when
