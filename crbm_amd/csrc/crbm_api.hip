@@ -1382,6 +1382,124 @@ int sweep_run(crbm_handle* h, const RowSource& src, int slab, int depth, Launch 
   return sweep_finish(h, src);
 }
 
+// ---- the stream sweep (crbm_scan_sites_codes, crbm_scan_histogram_codes) --------------------------------------------
+// What every feature over a stream of T codes (0..3 letters, 4 no letter) shares: a two-stream sweep over segments of
+// window starts (crbm_sweep.h, stream_plan: segment [start, start + cnt) needs letters [start, start + cnt + M - 1), a
+// halo of M - 1 behind its own).  Per segment, on its set's stream: the bytes go up (one per letter), scan_encode_kernel
+// makes letters and validity plane, then the feature's kernels run on the ScanInput the sweep hands it.  A generic DNA
+// model runs the kernels of its slab model, blockIdx.y = slab.  In order:
+//   admit()   the checks on the stream and the model, under the entry point's name; whose kernels run (kms, kjk)
+//   begin()   tables built, the segments planned, stage, letters and validity plane of every set sized for a whole
+//             segment; the feature then sizes what its own kernels write, before run()
+//   run()     launch(set, si, in, start, cnt) enqueues the feature's kernels; collect(...) copies that segment's outputs
+//             out on the set's stream, which the sweep then waits for: the set's buffers are free again.  `timing_env`
+//             set to 1: events around every segment's kernels, their sum on stderr.  At the end both streams are
+//             idle and a code above 4 anywhere in the stream is refused; a failed sweep is drained (sweep_drain).
+struct StreamSweep {
+  crbm_handle* h;
+  const char* api;                       // the entry point: named in its refusals and in its timing line
+  const ModelShape* kms = nullptr;       // whose kernels run: the model's own, or those of its slab model
+  const JitKernels* kjk = nullptr;
+  int M = 0, S = 0, nslab = 0;
+  StreamPlan plan{};
+
+  int admit(const uint8_t* codes, int64_t T) {
+    const std::string who = std::string(api) + ": ";
+    ARGCHK(T >= 0 && T <= (int64_t)INT32_MAX, "stream length must lie in [0, 2^31 - 1] (start is 32 bits wide)");
+    ARGCHK(codes || T == 0, "null argument");
+    ARGCHK(h->A == 4, who + "the alphabet must be DNA's (input_dims == 4)");
+    ARGCHK(h->ms().POOL == 1, who + "pooling > 1 is not supported (pool groups have no anchor in a stream)");
+    kms = h->big() ? &h->slab.ms : &h->ms();
+    kjk = h->big() ? &h->slab.jk : &h->jk;
+    ARGCHK((!h->big() || h->slab.K) && tab_bytes(*kms) <= 160 * 1024, who + "models that run on the generic kernels alone (motifs beyond 64 letters) are not supported");
+    M = h->M; S = h->ds ? 2 : 1; nslab = h->big() ? h->slab_n : 1;
+    return CRBM_OK;
+  }
+
+  int begin(int64_t T) {                 // T >= M
+    const int rc = sweep_begin(h);
+    if (rc) return rc;
+    plan = stream_plan((long)T, M, nslab, (size_t)env_int("CRBM_SLAB_BYTES", 256 << 20), getenv("CRBM_SLAB_BYTES") != nullptr);
+    for (int i = 0; i < plan.nsets; ++i) {
+      const SweepSet set = sweep_set(h, i);
+      HIPCHK(set.stage->ensure(((size_t)plan.seg + M - 1 + 3) / 4));
+      HIPCHK(set.letters->ensure((size_t)plan.full.letter_words));
+      HIPCHK(set.own->scan_valid.ensure((size_t)plan.full.valid_words));
+    }
+    return CRBM_OK;
+  }
+
+  template <class Launch, class Collect>
+  int run(const uint8_t* codes, const char* timing_env, Launch launch, Collect collect) {
+    const bool timing = env_int(timing_env, 0) != 0;
+    struct Events {                      // destroyed on every way out
+      hipEvent_t e[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+      ~Events() {
+        for (auto& set : e)
+          for (hipEvent_t ev : set)
+            if (ev) (void)hipEventDestroy(ev);
+      }
+    } events;
+    auto& tev = events.e;
+    double device_ms = 0.0;
+    int segments = 0;
+    if (timing)
+      for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
+    ScanInput in[2];
+    const int rc = run_slabs(plan.starts_all, plan.seg, 2,
+      [&](int, int si, int start, int cnt) -> int {
+        const SweepSet set = sweep_set(h, si);
+        const long n = (long)cnt + M - 1;                // (start + cnt <= T - M + 1: the halo is inside the stream)
+        const ScanLayout l = scan_layout(n, cnt);
+        HIPCHK(hipMemcpyAsync(set.stage->p, codes + start, (size_t)n, hipMemcpyHostToDevice, set.st));
+        if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
+        ScanEncodeArgs e;
+        e.codes = reinterpret_cast<const unsigned char*>(set.stage->p);
+        e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;
+        e.n = n; e.valid_words = l.valid_words;
+        hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
+        HIPCHK(hipGetLastError());
+        ScanInput& a = in[si];
+        a.tables = h->big() ? h->d_slab_tables : h->d_tables;
+        a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
+        a.starts = cnt; a.tiles = l.tiles; a.table_stride = kms->TABLES_ALL;
+        if (h->big()) a.plan = slab_plan(h);
+        else { a.plan.Ks = h->K; a.plan.K = h->K; a.plan.last_k0 = 0; }
+        const int r = launch(set, si, a, start, cnt);
+        if (!r && timing) HIPCHK(hipEventRecord(tev[si][1], set.st));
+        return r;
+      },
+      [&](int, int si, int start, int cnt) -> int {
+        const SweepSet set = sweep_set(h, si);
+        const int r = collect(set, si, in[si], start, cnt);
+        if (r) return r;
+        HIPCHK(hipStreamSynchronize(set.st));
+        if (timing) {
+          float ms = 0.f;
+          HIPCHK(hipEventElapsedTime(&ms, tev[si][0], tev[si][1]));
+          device_ms += ms;
+          ++segments;
+        }
+        return CRBM_OK;
+      },
+      [&] { sweep_drain(h); });
+    if (rc) return rc;
+    if (timing) fprintf(stderr, "%s: kernels %.3f ms over %d segments\n", api, device_ms, segments);
+    HIPCHK(hipStreamSynchronize(h->stream2));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    uint32_t flags = 0;
+    HIPCHK(hipMemcpyAsync(&flags, h->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (flags) {
+      HIPCHK(hipMemsetAsync(h->d_flags, 0, sizeof(uint32_t), h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+      return fail(h, CRBM_ERR_INVALID, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
+    }
+    return CRBM_OK;
+  }
+};
+
 }  // namespace
 
 // =============================================================================
@@ -2429,12 +2547,9 @@ int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64
 }
 
 // ---- stream scan (crbm_scan_sites_codes) ---------------------------------------------------------------------------
-// The sites of a stream of T codes (0..3 letters, 4 no letter), a two-stream sweep over segments of window starts:
-// segment [start, start + cnt) needs letters [start, start + cnt + M - 1), a halo of M - 1 behind its own.  Per segment
-// on the set's stream: the bytes go up (one per letter), scan_encode_kernel makes letters and validity plane,
-// crbm_scan_sites counts (pass 0), scan_offsets_kernel scans the tile counts, crbm_scan_sites writes the records at
-// their offsets (pass 1) -- in final order, so that a model on its own kernels is copied straight into the caller's
-// array.  A generic DNA model runs the kernel of its slab model, blockIdx.y = slab, every slab with its own counts,
+// The sites of a stream, a StreamSweep.  Per segment: crbm_scan_sites counts (pass 0), scan_offsets_kernel scans the
+// tile counts, crbm_scan_sites writes the records at their offsets (pass 1) -- in final order, so that a model on its
+// own kernels is copied straight into the caller's array.  Every slab of a generic DNA model has its own counts,
 // offsets and records; the slabs' runs, each sorted by start and owning ascending motifs, are merged on the host by
 // (start, slab).  Every set owns what it writes, sized for a whole segment before the sweep starts; only the records
 // may have to grow, as in motif_sites_any: pass 1 is then run again before anything is copied.  Since records are in
@@ -2445,109 +2560,56 @@ int scan_sites_any(crbm_handle* h, const uint8_t* codes, int64_t T, float thresh
   ARGCHK(threshold >= 0.f && threshold <= 1.f, "threshold must lie in [0, 1]");   // (NaN fails both)
   ARGCHK(capacity >= 0, "capacity must be >= 0");
   ARGCHK(sites || capacity == 0, "sites is required with a capacity");
-  ARGCHK(T >= 0 && T <= (int64_t)INT32_MAX, "stream length must lie in [0, 2^31 - 1] (start is 32 bits wide)");
-  ARGCHK(codes || T == 0, "null argument");
-  ARGCHK(h->A == 4, "crbm_scan_sites_codes: the alphabet must be DNA's (input_dims == 4)");
-  ARGCHK(h->ms().POOL == 1, "crbm_scan_sites_codes: pooling > 1 is not supported (pool groups have no anchor in a stream)");
-  // whose kernel runs: the model's own, or that of its slab model
-  const ModelShape& kms = h->big() ? h->slab.ms : h->ms();
-  const JitKernels& kjk = h->big() ? h->slab.jk : h->jk;
-  ARGCHK((!h->big() || h->slab.K) && tab_bytes(kms) <= 160 * 1024, "crbm_scan_sites_codes: models that run on the generic kernels alone (motifs beyond 64 letters) are not supported");
-  *count = 0;
-  const int M = h->M, S = h->ds ? 2 : 1;
-  if (T < M) return CRBM_OK;
-  const int starts_all = (int)(T - M + 1), nslab = h->big() ? h->slab_n : 1;
-  int rc = sweep_begin(h);
+  StreamSweep sw{h, "crbm_scan_sites_codes"};
+  int rc = sw.admit(codes, T);
   if (rc) return rc;
-  // a window start costs its staged byte, its letter and validity bits, per slab its counts and offsets, and a share of records
-  const size_t per_start = 4 + (size_t)4 * nslab;
-  int seg = slab_rows(starts_all, per_start);
-  if (!getenv("CRBM_SLAB_BYTES")) seg = (int)std::min<size_t>((size_t)seg, std::max<size_t>(1, (32u << 20) / per_start));
+  *count = 0;
+  if (T < sw.M) return CRBM_OK;
+  rc = sw.begin(T);
+  if (rc) return rc;
+  const int nslab = sw.nslab, seg = sw.plan.seg, full_tiles = sw.plan.full.tiles;
   const bool want_recs = capacity > 0;
-  const ScanLayout lay = scan_layout((long)seg + M - 1, seg);
   size_t rcap[2] = {0, 0};                               // records per slab a set's buffer is used for
-  const int nsets = seg < starts_all ? 2 : 1;
-  for (int i = 0; i < nsets; ++i) {                      // everything both streams write, at its size, before either starts
+  for (int i = 0; i < sw.plan.nsets; ++i) {              // everything both streams write, at its size, before either starts
     const SweepSet set = sweep_set(h, i);
-    HIPCHK(set.stage->ensure(((size_t)seg + M - 1 + 3) / 4));
-    HIPCHK(set.letters->ensure((size_t)lay.letter_words));
-    HIPCHK(set.own->scan_valid.ensure((size_t)lay.valid_words));
-    HIPCHK(set.own->scan_lanes.ensure((size_t)nslab * 64 * lay.tiles));
-    HIPCHK(set.own->scan_tiles.ensure((size_t)nslab * lay.tiles));
-    HIPCHK(set.own->scan_off.ensure((size_t)nslab * lay.tiles + nslab));
+    HIPCHK(set.own->scan_lanes.ensure((size_t)nslab * 64 * full_tiles));
+    HIPCHK(set.own->scan_tiles.ensure((size_t)nslab * full_tiles));
+    HIPCHK(set.own->scan_off.ensure((size_t)nslab * full_tiles + nslab));
     if (want_recs) {
-      rcap[i] = (size_t)std::min<unsigned long long>({(unsigned long long)capacity, (unsigned long long)seg * kms.K * S,
+      rcap[i] = (size_t)std::min<unsigned long long>({(unsigned long long)capacity, (unsigned long long)seg * sw.kms->K * sw.S,
                                                      std::max<unsigned long long>(1ull << 16, (unsigned long long)seg / 4)});
       HIPCHK(set.own->site_recs.ensure(rcap[i] * nslab));
     }
   }
-  auto scan_args = [&](const SweepSet& set, int si, int start, int cnt, int pass) {
-    const ScanLayout l = scan_layout((long)cnt + M - 1, cnt);
-    ScanArgs a;
-    a.tables = h->big() ? h->d_slab_tables : h->d_tables;
-    a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
+  auto launch_pass = [&](const SweepSet& set, int si, const ScanInput& in, int start, int pass) -> int {
+    ScanArgs a{in};
     a.lane_cnt = set.own->scan_lanes.p; a.tile_cnt = set.own->scan_tiles.p; a.tile_off = set.own->scan_off.p;
     a.recs = set.own->site_recs.p; a.capacity = rcap[si];
-    a.starts = cnt; a.tiles = l.tiles; a.pos0 = start; a.pass = pass; a.threshold = threshold;
-    a.table_stride = kms.TABLES_ALL;
-    if (h->big()) a.plan = slab_plan(h);
-    else { a.plan.Ks = h->K; a.plan.K = h->K; a.plan.last_k0 = 0; }
-    return a;
-  };
-  auto launch_pass = [&](const SweepSet& set, int si, int start, int cnt, int pass) -> int {
-    const ScanArgs a = scan_args(set, si, start, cnt, pass);
-    const unsigned gx = (unsigned)std::max(1, std::min((a.tiles + 3) / 4, std::max(1, h->num_cu * 8 / nslab)));
-    HIPCHK(jit_launch(kjk.scan_sites, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(kms), set.st));
+    a.pos0 = start; a.pass = pass; a.threshold = threshold; a.pad_ = 0;
+    const unsigned gx = (unsigned)std::max(1, std::min((in.tiles + 3) / 4, std::max(1, h->num_cu * 8 / nslab)));
+    HIPCHK(jit_launch(sw.kjk->scan_sites, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(*sw.kms), set.st));
     return CRBM_OK;
   };
   int64_t total = 0;
   bool wrote[2] = {false, false};                        // the set's segment went through pass 1
-  // CRBM_SCAN_TIMING=1 (tools/bench_scan.py): events around every segment's kernels, their sum on stderr
-  const bool timing = env_int("CRBM_SCAN_TIMING", 0) != 0;
-  hipEvent_t tev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-  double device_ms = 0.0;
-  int segments = 0;
-  if (timing)
-    for (int i = 0; i < 2; ++i)
-      for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
   std::vector<unsigned long long> tot((size_t)nslab);
   std::vector<std::vector<SiteRec>> runs((size_t)(nslab > 1 ? nslab : 0));
-  rc = run_slabs(starts_all, seg, 2,
-    [&](int, int si, int start, int cnt) -> int {
-      const SweepSet set = sweep_set(h, si);
-      const long n = (long)cnt + M - 1;                  // (start + cnt <= T - M + 1: the halo is inside the stream)
-      const ScanLayout l = scan_layout(n, cnt);
-      HIPCHK(hipMemcpyAsync(set.stage->p, codes + start, (size_t)n, hipMemcpyHostToDevice, set.st));
-      if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
-      ScanEncodeArgs e;
-      e.codes = reinterpret_cast<const unsigned char*>(set.stage->p);
-      e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;
-      e.n = n; e.valid_words = l.valid_words;
-      hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
-      HIPCHK(hipGetLastError());
-      int r = launch_pass(set, si, start, cnt, 0);
+  // CRBM_SCAN_TIMING=1: tools/bench_scan.py
+  rc = sw.run(codes, "CRBM_SCAN_TIMING",
+    [&](const SweepSet& set, int si, const ScanInput& in, int start, int) -> int {
+      int r = launch_pass(set, si, in, start, 0);
       if (r) return r;
       ScanOffsetsArgs o;
       o.tile_cnt = set.own->scan_tiles.p; o.tile_off = set.own->scan_off.p;
-      o.total = set.own->scan_off.p + (size_t)nslab * l.tiles; o.tiles = l.tiles;
+      o.total = set.own->scan_off.p + (size_t)nslab * in.tiles; o.tiles = in.tiles;
       hipLaunchKernelGGL(scan_offsets_kernel, dim3(nslab), dim3(1024), 1024 * sizeof(unsigned long long), set.st, o);
       HIPCHK(hipGetLastError());
       wrote[si] = want_recs && total < capacity;         // (`total` lags by one segment and only grows: never skipped wrongly)
-      r = wrote[si] ? launch_pass(set, si, start, cnt, 1) : CRBM_OK;
-      if (!r && timing) HIPCHK(hipEventRecord(tev[si][1], set.st));
-      return r;
+      return wrote[si] ? launch_pass(set, si, in, start, 1) : CRBM_OK;
     },
-    [&](int, int si, int start, int cnt) -> int {
-      const SweepSet set = sweep_set(h, si);
-      const ScanLayout l = scan_layout((long)cnt + M - 1, cnt);
-      HIPCHK(hipMemcpyAsync(tot.data(), set.own->scan_off.p + (size_t)nslab * l.tiles, (size_t)nslab * 8, hipMemcpyDeviceToHost, set.st));
+    [&](const SweepSet& set, int si, const ScanInput& in, int start, int) -> int {
+      HIPCHK(hipMemcpyAsync(tot.data(), set.own->scan_off.p + (size_t)nslab * in.tiles, (size_t)nslab * 8, hipMemcpyDeviceToHost, set.st));
       HIPCHK(hipStreamSynchronize(set.st));
-      if (timing) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, tev[si][0], tev[si][1]));
-        device_ms += ms;
-        ++segments;
-      }
       unsigned long long c = 0, most = 0;
       for (int y = 0; y < nslab; ++y) c += tot[y];
       if (wrote[si] && total < capacity && c > 0) {
@@ -2556,7 +2618,7 @@ int scan_sites_any(crbm_handle* h, const uint8_t* codes, int64_t T, float thresh
         if (most > rcap[si]) {        // more records than the set's buffer took: pass 1 again, into one that takes them
           HIPCHK(set.own->site_recs.ensure((size_t)most * nslab));
           rcap[si] = (size_t)most;
-          const int r = launch_pass(set, si, start, cnt, 1);
+          const int r = launch_pass(set, si, in, start, 1);
           if (r) return r;
         }
         if (nslab == 1) {
@@ -2581,143 +2643,57 @@ int scan_sites_any(crbm_handle* h, const uint8_t* codes, int64_t T, float thresh
       }
       total += (int64_t)c;
       return CRBM_OK;
-    },
-    [&] { sweep_drain(h); });
-  if (timing) {
-    for (int i = 0; i < 2; ++i)
-      for (int j = 0; j < 2; ++j) (void)hipEventDestroy(tev[i][j]);
-    if (!rc) fprintf(stderr, "crbm_scan_sites_codes: kernels %.3f ms over %d segments\n", device_ms, segments);
-  }
+    });
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream2));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  uint32_t flags = 0;
-  HIPCHK(hipMemcpyAsync(&flags, h->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (flags) {
-    HIPCHK(hipMemsetAsync(h->d_flags, 0, sizeof(uint32_t), h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return fail(h, CRBM_ERR_INVALID, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
-  }
   *count = total;
   return CRBM_OK;
 }
 
 // ---- score histogram (crbm_scan_histogram_codes) --------------------------------------------------------------------
-// scan_sites_any's sweep -- the same segments, halo, sets and slab budget -- with crbm_scan_hist in place of the two
-// passes: bytes up, scan_encode_kernel, one launch that adds the segment's scores into h->hist.  The histogram is
+// A StreamSweep with one launch per segment: crbm_scan_hist adds the segment's scores into h->hist.  The histogram is
 // zeroed on the main stream, which is then waited for, before the first segment; both streams add into it with
 // integer atomics; it is copied back once, after both streams are idle.  A segment has nothing to collect.
 // CRBM_HIST_VARIANT picks how a wave spreads its LDS adds (scan_hist_body: 0 in order, 1 lane-rotated motif order,
-// 2 counter sets per wave); CRBM_HIST_TIMING=1 (tools/bench_calibrate.py) puts events around every segment's kernels
-// and their sum on stderr.
+// 2 counter sets per wave); CRBM_HIST_TIMING=1: tools/bench_calibrate.py.
 int scan_hist_any(crbm_handle* h, const uint8_t* codes, int64_t T, float lo, float hi, int32_t nbins, uint64_t* counts,
                   int64_t* windows) {
   ARGCHK(counts, "null argument");
   ARGCHK(nbins >= 1 && nbins <= 1024, "nbins must lie in [1, 1024]");
   ARGCHK(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "lo and hi must be finite with lo < hi");
-  ARGCHK(T >= 0 && T <= (int64_t)INT32_MAX, "stream length must lie in [0, 2^31 - 1]");
-  ARGCHK(codes || T == 0, "null argument");
-  ARGCHK(h->A == 4, "crbm_scan_histogram_codes: the alphabet must be DNA's (input_dims == 4)");
-  ARGCHK(h->ms().POOL == 1, "crbm_scan_histogram_codes: pooling > 1 is not supported (pool groups have no anchor in a stream)");
-  const ModelShape& kms = h->big() ? h->slab.ms : h->ms();
-  const JitKernels& kjk = h->big() ? h->slab.jk : h->jk;
-  ARGCHK((!h->big() || h->slab.K) && tab_bytes(kms) <= 160 * 1024, "crbm_scan_histogram_codes: models that run on the generic kernels alone (motifs beyond 64 letters) are not supported");
-  const int M = h->M, S = h->ds ? 2 : 1;
+  StreamSweep sw{h, "crbm_scan_histogram_codes"};
+  int rc = sw.admit(codes, T);
+  if (rc) return rc;
+  const int nslab = sw.nslab;
   const int variant = env_int("CRBM_HIST_VARIANT", 1);
-  const HistPlan hp = hist_plan(tab_bytes(kms), kms.NQ, S, nbins, variant == 2 ? 8 : 1);
+  const HistPlan hp = hist_plan(tab_bytes(*sw.kms), sw.kms->NQ, sw.S, nbins, variant == 2 ? 8 : 1);
   ARGCHK(hp.gq >= 1, "crbm_scan_histogram_codes: the counters of four motifs do not fit beside the model's gather table (fewer bins)");
   const float inv_w = (float)nbins / (hi - lo);
   ARGCHK(std::isfinite(inv_w) && inv_w > 0.f, "hi - lo is too small or too large for nbins");
-  const size_t cells = (size_t)h->K * S * nbins;
-  if (T < M) {
+  const size_t cells = (size_t)h->K * sw.S * nbins;
+  if (T < sw.M) {
     std::memset(counts, 0, cells * sizeof(uint64_t));
     if (windows) *windows = 0;
     return CRBM_OK;
   }
-  const int starts_all = (int)(T - M + 1), nslab = h->big() ? h->slab_n : 1;
-  int rc = sweep_begin(h);
+  rc = sw.begin(T);
   if (rc) return rc;
-  const size_t per_start = 4 + (size_t)4 * nslab;          // scan_sites_any's figure: the same segments for the same budget
-  int seg = slab_rows(starts_all, per_start);
-  if (!getenv("CRBM_SLAB_BYTES")) seg = (int)std::min<size_t>((size_t)seg, std::max<size_t>(1, (32u << 20) / per_start));
-  const ScanLayout lay = scan_layout((long)seg + M - 1, seg);
-  const int nsets = seg < starts_all ? 2 : 1;
-  for (int i = 0; i < nsets; ++i) {
-    const SweepSet set = sweep_set(h, i);
-    HIPCHK(set.stage->ensure(((size_t)seg + M - 1 + 3) / 4));
-    HIPCHK(set.letters->ensure((size_t)lay.letter_words));
-    HIPCHK(set.own->scan_valid.ensure((size_t)lay.valid_words));
-  }
   HIPCHK(h->hist.ensure(cells + 1));
   HIPCHK(hipMemsetAsync(h->hist.p, 0, (cells + 1) * sizeof(unsigned long long), h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));                 // zero before either stream adds
-  const bool timing = env_int("CRBM_HIST_TIMING", 0) != 0;
-  struct Events {                                          // destroyed on every way out
-    hipEvent_t e[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    ~Events() {
-      for (auto& set : e)
-        for (hipEvent_t ev : set)
-          if (ev) (void)hipEventDestroy(ev);
-    }
-  } events;
-  auto& tev = events.e;
-  double device_ms = 0.0;
-  int segments = 0;
-  if (timing)
-    for (int i = 0; i < 2; ++i)
-      for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
-  rc = run_slabs(starts_all, seg, 2,
-    [&](int, int si, int start, int cnt) -> int {
-      const SweepSet set = sweep_set(h, si);
-      const long n = (long)cnt + M - 1;
-      const ScanLayout l = scan_layout(n, cnt);
-      HIPCHK(hipMemcpyAsync(set.stage->p, codes + start, (size_t)n, hipMemcpyHostToDevice, set.st));
-      if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
-      ScanEncodeArgs e;
-      e.codes = reinterpret_cast<const unsigned char*>(set.stage->p);
-      e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;
-      e.n = n; e.valid_words = l.valid_words;
-      hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
-      HIPCHK(hipGetLastError());
-      ScanHistArgs a;
-      a.tables = h->big() ? h->d_slab_tables : h->d_tables;
-      a.letters = set.letters->p; a.valid = set.own->scan_valid.p; a.hist = h->hist.p;
-      a.starts = cnt; a.tiles = l.tiles; a.nbins = nbins; a.gq = hp.gq; a.copies = hp.copies; a.rotate = variant == 1;
-      a.lo = lo; a.inv_w = inv_w; a.table_stride = kms.TABLES_ALL;
-      if (h->big()) a.plan = slab_plan(h);
-      else { a.plan.Ks = h->K; a.plan.K = h->K; a.plan.last_k0 = 0; }
+  rc = sw.run(codes, "CRBM_HIST_TIMING",
+    [&](const SweepSet& set, int, const ScanInput& in, int, int) -> int {
+      ScanHistArgs a{in};
+      a.hist = h->hist.p;
+      a.nbins = nbins; a.gq = hp.gq; a.copies = hp.copies; a.rotate = variant == 1;
+      a.lo = lo; a.inv_w = inv_w;
       // eight waves a block; as many blocks as the CUs hold at this LDS footprint, each with at least two tiles a wave
       const int per_cu = (int)std::max<long>(1, std::min<long>(4, 160L * 1024 / hp.lds));
-      const unsigned gx = (unsigned)std::max(1, std::min((a.tiles + 15) / 16, std::max(1, h->num_cu * per_cu / nslab)));
-      HIPCHK(jit_launch(kjk.scan_hist, a, gx, (unsigned)nslab, 512, (unsigned)hp.lds, set.st));
-      if (timing) HIPCHK(hipEventRecord(tev[si][1], set.st));
+      const unsigned gx = (unsigned)std::max(1, std::min((in.tiles + 15) / 16, std::max(1, h->num_cu * per_cu / nslab)));
+      HIPCHK(jit_launch(sw.kjk->scan_hist, a, gx, (unsigned)nslab, 512, (unsigned)hp.lds, set.st));
       return CRBM_OK;
     },
-    [&](int, int si, int, int) -> int {
-      const SweepSet set = sweep_set(h, si);
-      HIPCHK(hipStreamSynchronize(set.st));               // the set's buffers are free again
-      if (timing) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, tev[si][0], tev[si][1]));
-        device_ms += ms;
-        ++segments;
-      }
-      return CRBM_OK;
-    },
-    [&] { sweep_drain(h); });
-  if (timing && !rc) fprintf(stderr, "crbm_scan_histogram_codes: kernels %.3f ms over %d segments\n", device_ms, segments);
+    [](const SweepSet&, int, const ScanInput&, int, int) -> int { return CRBM_OK; });
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream2));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  uint32_t flags = 0;
-  HIPCHK(hipMemcpyAsync(&flags, h->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (flags) {
-    HIPCHK(hipMemsetAsync(h->d_flags, 0, sizeof(uint32_t), h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return fail(h, CRBM_ERR_INVALID, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
-  }
   std::vector<unsigned long long> out(cells + 1);
   HIPCHK(hipMemcpyAsync(out.data(), h->hist.p, (cells + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));

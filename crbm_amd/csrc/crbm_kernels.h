@@ -981,6 +981,14 @@ __device__ __forceinline__ void conv_gather_quads(const float* T, const LetterWi
     for (int g = 1; g < C::NG; ++g) group(g, IC<0>{});
   }
 }
+// THE WINDOW CORE: z[] of motifs [4 q0, 4 q0 + 4 NQW) for window `w` on `strand` (1: its reverse complement).
+// Single-stranded models score sigma(x + x') (convRBM.py:511-514): the other orientation is added on top, one strand.
+// motif_sites_body, scan_sites_body and scan_hist_body all score through this one function: the same bits.
+template <class C, int NQW>
+__device__ __forceinline__ void window_strand_z(const float* Tf, const LetterWin<C::M>& w, int q0, int strand, float (&z)[4 * NQW]) {
+  conv_gather_quads<C, NQW>(Tf, strand ? revcomp_window<C::M>(w) : w, q0, z);
+  if (!C::DS) conv_gather_quads<C, NQW, true>(Tf, revcomp_window<C::M>(w), q0, z);
+}
 
 // One 32-position group (slot 0 or 1 of the wave's unit): all accumulator tiles of the wave.
 //   Pt  : the wave's column image (row kind*KW + i, stride STATS_RS, position slot*32 + t)
@@ -2150,7 +2158,6 @@ template <class C>
 __device__ void motif_sites_body(const SitesArgs& a) {
   constexpr int K = C::K, M = C::M, NI = C::HIT_NI, PC = 64 * NI;
   constexpr int NQW = C::NQ < 4 ? C::NQ : 4, NV = 4 * NQW;
-  constexpr bool BOTH = !C::DS;   // single-stranded models score sigma(x + x'), convRBM.py:511-514
   constexpr int S = C::DS ? 2 : 1;
   HIP_DYNAMIC_SHARED(float, smem);
   float* Tf = smem;
@@ -2167,11 +2174,7 @@ __device__ void motif_sites_body(const SitesArgs& a) {
 #pragma unroll
       for (int j = 0; j < NV; ++j) p[j] = 0.f;
       if (s >= a.Lh) return;
-      auto zfun = [&](int pos, float (&zz)[NV]) {
-        const LetterWin<M> w = letter_window<M>(row, pos);
-        conv_gather_quads<C, NQW>(Tf, strand ? revcomp_window<M>(w) : w, q0, zz);
-        if (BOTH) conv_gather_quads<C, NQW, true>(Tf, revcomp_window<M>(w), q0, zz);
-      };
+      auto zfun = [&](int pos, float (&zz)[NV]) { window_strand_z<C, NQW>(Tf, letter_window<M>(row, pos), q0, strand, zz); };
       if constexpr (C::POOL > 1) {
         float cb[NV], Sg[NV];
         pooled_probs<C::POOL, NV>(zfun, s, p, cb, Sg);
@@ -2858,6 +2861,40 @@ struct SlabPlan {
   int32_t Ks, K, last_k0;     // motifs per slab, motifs of the model, first motif of the last slab (it may overlap its neighbour)
 };
 __device__ __forceinline__ int slab_k0(const SlabPlan& p, int y) { return (y + 1) * p.Ks <= p.K ? y * p.Ks : p.last_k0; }
+// Slab y owns motifs [k0 + kskip, k0 + kend) of the model, [kskip, kend) of its kernel: those below kskip belong to the
+// neighbouring slab as well and are reported there; those from kend on lie past the model.
+struct SlabSpan {
+  int k0, kskip, kend;
+};
+template <class C>
+__device__ __forceinline__ SlabSpan slab_span(const SlabPlan& p, int y) {
+  SlabSpan s;
+  s.k0 = slab_k0(p, y);
+  s.kskip = y > 0 ? max(0, slab_k0(p, y - 1) + p.Ks - s.k0) : 0;
+  s.kend = min(C::K, p.K - s.k0);      // (C::K == p.Ks)
+  return s;
+}
+// What every stream kernel reads (scan_sites_body, scan_hist_body): one segment of a stream as scan_encode_kernel left
+// it (crbm_layout.h, scan_layout) and the model's slabs.  Filled in one place per driver (crbm_api.hip, StreamSweep);
+// 48 bytes, no padding: it travels by value as the base of the kernels' argument structs.
+struct ScanInput {
+  const float* tables;                 // the first slab's image
+  const uint32_t* letters;
+  const unsigned long long* valid;
+  int32_t starts, tiles;               // window starts of the segment, tiles of 64 of them
+  int32_t table_stride;                // floats
+  SlabPlan plan;
+};
+static_assert(sizeof(ScanInput) == 48, "ScanInput has no padding");
+// all M validity bits from window start s on (the plane has two zero words behind: s >> 6 and the next one are inside)
+template <int M>
+__device__ __forceinline__ bool window_valid(const unsigned long long* valid, int s) {
+  const int sh = s & 63;
+  const unsigned long long v0 = valid[s >> 6], v1 = valid[(s >> 6) + 1];
+  const unsigned long long v = sh ? (v0 >> sh) | (v1 << (64 - sh)) : v0;
+  const unsigned long long need = M < 64 ? (1ull << M) - 1ull : ~0ull;
+  return (v & need) == need;
+}
 
 struct SlabTablesArgs {
   TablesArgs t;               // W, b of the whole model; out: the first slab's image
@@ -2896,11 +2933,12 @@ struct SlabHgvArgs {
 template <class C>
 __device__ void slab_hgv_body(const SlabHgvArgs& s) {
   HgvMasksArgs ma = s.m;
-  const int y = (int)blockIdx.y, k0 = slab_k0(s.plan, y);
+  const int y = (int)blockIdx.y;
+  const SlabSpan span = slab_span<C>(s.plan, y);
   ma.g.tables += (size_t)y * s.table_stride;
-  ma.k0 = k0;
-  ma.group0 = (uint32_t)(k0 / 10);
-  ma.kskip = y > 0 ? max(0, slab_k0(s.plan, y - 1) + s.plan.Ks - k0) : 0;     // units the neighbouring slab counts
+  ma.k0 = span.k0;
+  ma.group0 = (uint32_t)(span.k0 / 10);
+  ma.kskip = span.kskip;               // units the neighbouring slab counts
   hgv_masks_body<C>(ma);
 }
 
@@ -2924,7 +2962,7 @@ __device__ void slab_fe_body(const SlabFeArgs& s) {
 // ===========================================================================
 // Stream scan (crbm_scan_sites_codes): the sites of a 1-D stream of letters in which some positions hold no letter.
 // A window [s, s + M) is valid when all of its M positions hold letters; a valid window scores exactly like the same
-// M letters in a row of motif_sites_body (the same gather calls in the same order: the same bits); an invalid one
+// M letters in a row of motif_sites_body (both score through window_strand_z: the same bits); an invalid one
 // yields nothing.  The segment arrives as 2-bit letter words and a validity plane (crbm_layout.h, scan_layout;
 // scan_encode_kernel).  A block keeps the gather table in LDS; a wave walks tiles of 64 window starts, a lane owns one.
 // Records leave the device in their final order -- (start, motif, strand), + before - -- in two passes of this body:
@@ -2936,21 +2974,16 @@ __device__ void slab_fe_body(const SlabFeArgs& s) {
 // blockIdx.y is the slab of a generic DNA model (its table image, its motifs [k0 + kskip, min(k0 + Ks, K)), its part of
 // every buffer); a model on its own kernels is one slab of all its motifs.
 // ===========================================================================
-struct ScanArgs {
-  const float* tables;                 // the first slab's image
-  const uint32_t* letters;
-  const unsigned long long* valid;
+struct ScanArgs : ScanInput {
   unsigned short* lane_cnt;            // [slab][64 * tiles]
   uint32_t* tile_cnt;                  // [slab][tiles]
   const unsigned long long* tile_off;  // [slab][tiles], pass 1
   SiteRec* recs;                       // [slab][capacity], pass 1
   unsigned long long capacity;         // records per slab
-  int32_t starts, tiles;               // window starts of the segment, tiles of 64 of them
   int32_t pos0;                        // stream position of the segment's first letter
   int32_t pass;
   float threshold;
-  int32_t table_stride;                // floats
-  SlabPlan plan;
+  int32_t pad_;
 };
 // sum over the wave and over the lower lanes of a small per-lane count (< 2^BITS), bit plane by bit plane (all lanes call it)
 template <int BITS>
@@ -2969,42 +3002,33 @@ __device__ void scan_sites_body(const ScanArgs& a) {
   if constexpr (C::POOL == 1) {       // pool groups have no anchor in a stream: refused on the host, no body
     constexpr int M = C::M, S = C::DS ? 2 : 1;
     constexpr int NQW = C::NQ < 4 ? C::NQ : 4, NV = 4 * NQW;
-    constexpr bool BOTH = !C::DS;     // single-stranded models score sigma(x + x'), as motif_sites_body
     static_assert(C::K * S < (1 << 10), "a lane's count must fit ten bits");
     HIP_DYNAMIC_SHARED(float, smem);
     float* Tf = smem;
-    const int y = (int)blockIdx.y, k0 = slab_k0(a.plan, y);
-    const int kskip = y > 0 ? max(0, slab_k0(a.plan, y - 1) + a.plan.Ks - k0) : 0;   // motifs the neighbouring slab reports
-    const int kend = min(C::K, a.plan.K - k0);
-    copy_tables<C::TAB>(Tf, a.tables + (size_t)y * a.table_stride + C::OFF_TF);
+    const ScanInput& in = a;
+    const int y = (int)blockIdx.y;
+    const SlabSpan span = slab_span<C>(in.plan, y);
+    copy_tables<C::TAB>(Tf, in.tables + (size_t)y * in.table_stride + C::OFF_TF);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const float thr = a.threshold;
-    unsigned short* lane_cnt = a.lane_cnt + (size_t)y * 64 * a.tiles;
-    uint32_t* tile_cnt = a.tile_cnt + (size_t)y * a.tiles;
-    // p[] = the scores of motifs [4 q0, 4 q0 + NV) of the window on `strand`: motif_sites_body's gather, to the instruction
+    unsigned short* lane_cnt = a.lane_cnt + (size_t)y * 64 * in.tiles;
+    uint32_t* tile_cnt = a.tile_cnt + (size_t)y * in.tiles;
+    // p[] = the scores of motifs [4 q0, 4 q0 + NV) of the window on `strand`
     auto scores = [&](const LetterWin<M>& w, int q0, int strand, float (&p)[NV]) {
       float z[NV];
-      conv_gather_quads<C, NQW>(Tf, strand ? revcomp_window<M>(w) : w, q0, z);
-      if (BOTH) conv_gather_quads<C, NQW, true>(Tf, revcomp_window<M>(w), q0, z);
+      window_strand_z<C, NQW>(Tf, w, q0, strand, z);
 #pragma unroll
       for (int j = 0; j < NV; ++j) p[j] = sigmoid_z(z[j]);
     };
-    auto is_hit = [&](int kk, float p) { return kk >= kskip && kk < kend && p >= thr; };
-    for (int t = blockIdx.x * nwaves + wave; t < a.tiles; t += gridDim.x * nwaves) {
+    auto is_hit = [&](int kk, float p) { return kk >= span.kskip && kk < span.kend && p >= thr; };
+    for (int t = blockIdx.x * nwaves + wave; t < in.tiles; t += gridDim.x * nwaves) {
       const int s = 64 * t + lane;
       if (a.pass == 0) {
-        bool ok = s < a.starts;
-        if (ok) {                     // all M validity bits from s on
-          const int sh = s & 63;
-          const unsigned long long v0 = a.valid[s >> 6], v1 = a.valid[(s >> 6) + 1];
-          const unsigned long long v = sh ? (v0 >> sh) | (v1 << (64 - sh)) : v0;
-          const unsigned long long need = M < 64 ? (1ull << M) - 1ull : ~0ull;
-          ok = (v & need) == need;
-        }
+        const bool ok = s < in.starts && window_valid<M>(in.valid, s);
         uint32_t c = 0;
         if (ok) {
-          const LetterWin<M> w = letter_window<M>(a.letters, s);
+          const LetterWin<M> w = letter_window<M>(in.letters, s);
 #pragma unroll 1
           for (int q0 = 0; q0 < C::NQ; q0 += NQW)
 #pragma unroll 1
@@ -3024,9 +3048,9 @@ __device__ void scan_sites_body(const ScanArgs& a) {
         const uint32_t c = lane_cnt[s];
         uint32_t below, total;
         wave_count_sums<10>(c, below, total);
-        unsigned long long idx = a.tile_off[(size_t)y * a.tiles + t] + below;
+        unsigned long long idx = a.tile_off[(size_t)y * in.tiles + t] + below;
         SiteRec* recs = a.recs + (size_t)y * a.capacity;
-        const LetterWin<M> w = letter_window<M>(a.letters, s);
+        const LetterWin<M> w = letter_window<M>(in.letters, s);
 #pragma unroll 1
         for (int q0 = 0; q0 < (c ? C::NQ : 0); q0 += NQW) {   // lanes without hits sit the tile out
           float p[S][NV];
@@ -3039,7 +3063,7 @@ __device__ void scan_sites_body(const ScanArgs& a) {
               if (is_hit(4 * q0 + j, p[strand][j])) {
                 if (idx < a.capacity) {
                   SiteRec* d = recs + idx;
-                  d->seq = 0; d->motif = k0 + 4 * q0 + j; d->start = a.pos0 + s;
+                  d->seq = 0; d->motif = span.k0 + 4 * q0 + j; d->start = a.pos0 + s;
                   d->strand = C::DS ? (strand ? -1 : 1) : 0; d->prob = p[strand][j];
                 }
                 ++idx;
@@ -3052,8 +3076,8 @@ __device__ void scan_sites_body(const ScanArgs& a) {
 
 // ===========================================================================
 // Score histogram (crbm_scan_histogram_codes): the stream scan with a histogram per (motif, strand) in place of records.
-// Same input, tiles and slabs as scan_sites_body; the score of a valid window is the log-odds x = x_of_z(z) of the z
-// the scan's gather returns (the same calls in the same order; single-stranded models: z summed over both
+// Same input (ScanInput), tiles and slabs as scan_sites_body; the score of a valid window is the log-odds
+// x = x_of_z(z) of the z the scan scores with (window_strand_z; single-stranded models: z summed over both
 // orientations, one strand), so that sigmoid(x) is the probability the scan reports.
 // THE BIN RULE: t = (x - lo) * inv_w with inv_w = nbins / (hi - lo) formed on the host in fp32; the bin is 0 for
 // t < 0, nbins - 1 for t >= nbins, (int)t otherwise -- the first bin holds everything below lo, the last everything at
@@ -3068,19 +3092,13 @@ __device__ void scan_sites_body(const ScanArgs& a) {
 //   variant 1  lane l starts at motif l mod NV (a select tree over the NV counter addresses per step);
 //   variant 2  as 0 with `copies` counter sets, wave w adds into set w mod copies.
 // ===========================================================================
-struct ScanHistArgs {
-  const float* tables;                 // the first slab's image
-  const uint32_t* letters;
-  const unsigned long long* valid;
+struct ScanHistArgs : ScanInput {
   unsigned long long* hist;            // [K][S][nbins], then the valid windows
-  int32_t starts, tiles;               // window starts of the segment, tiles of 64 of them
   int32_t nbins;
   int32_t gq;                          // motif quads whose counters the LDS holds: a multiple of the gather's quads, or fewer
   int32_t copies;                      // counter sets (variant 2; else 1)
   int32_t rotate;                      // variant 1
   float lo, inv_w;
-  int32_t table_stride;                // floats
-  SlabPlan plan;
 };
 // v[j] for a lane-dependent j in [0, N): a tree of selects, no indexed register access
 template <int N>
@@ -3104,16 +3122,15 @@ __device__ void scan_hist_body(const ScanHistArgs& a) {
   if constexpr (C::POOL == 1) {       // refused on the host, as the scan
     constexpr int M = C::M, S = C::DS ? 2 : 1;
     constexpr int NQW = C::NQ < 4 ? C::NQ : 4, NV = 4 * NQW;
-    constexpr bool BOTH = !C::DS;
     HIP_DYNAMIC_SHARED(float, smem);
     float* Tf = smem;
     uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + C::TAB);    // [copies][4 gq][S][nbins], then the block's valid windows
-    const int y = (int)blockIdx.y, k0 = slab_k0(a.plan, y);
-    const int kskip = y > 0 ? max(0, slab_k0(a.plan, y - 1) + a.plan.Ks - k0) : 0;   // motifs the neighbouring slab counts
-    const int kend = min(C::K, a.plan.K - k0);
+    const ScanInput& in = a;
+    const int y = (int)blockIdx.y;
+    const SlabSpan span = slab_span<C>(in.plan, y);
     const int nb = a.nbins, row = S * nb, per = 4 * a.gq * row;    // counters of a motif, of a counter set
     uint32_t* wcnt = cnt + (size_t)a.copies * per;
-    copy_tables<C::TAB>(Tf, a.tables + (size_t)y * a.table_stride + C::OFF_TF);
+    copy_tables<C::TAB>(Tf, in.tables + (size_t)y * in.table_stride + C::OFF_TF);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     uint32_t* mine = cnt + (size_t)(wave % a.copies) * per;
     const float lo = a.lo, inv_w = a.inv_w, nbf = (float)nb;
@@ -3122,36 +3139,28 @@ __device__ void scan_hist_body(const ScanHistArgs& a) {
       const int g1 = min(g0 + a.gq, C::NQ);
       for (int i = threadIdx.x; i < a.copies * per + (g0 == 0 ? 1 : 0); i += blockDim.x) cnt[i] = 0u;
       __syncthreads();                 // (the first one also stands behind copy_tables)
-      for (int t = blockIdx.x * nwaves + wave; t < a.tiles; t += gridDim.x * nwaves) {
+      for (int t = blockIdx.x * nwaves + wave; t < in.tiles; t += gridDim.x * nwaves) {
         const int s = 64 * t + lane;
-        bool ok = s < a.starts;
-        if (ok) {                      // all M validity bits from s on, as scan_sites_body
-          const int sh = s & 63;
-          const unsigned long long v0 = a.valid[s >> 6], v1 = a.valid[(s >> 6) + 1];
-          const unsigned long long v = sh ? (v0 >> sh) | (v1 << (64 - sh)) : v0;
-          const unsigned long long need = M < 64 ? (1ull << M) - 1ull : ~0ull;
-          ok = (v & need) == need;
-        }
+        const bool ok = s < in.starts && window_valid<M>(in.valid, s);
         if (g0 == 0 && y == 0) {       // wave-uniform
           const unsigned long long m = __ballot(ok);
           if (lane == 0 && m) atomicAdd(wcnt, (uint32_t)__popcll(m));
         }
         if (!ok) continue;
-        const LetterWin<M> w = letter_window<M>(a.letters, s);
+        const LetterWin<M> w = letter_window<M>(in.letters, s);
 #pragma unroll 1
         for (int q0 = (g0 / NQW) * NQW; q0 < g1; q0 += NQW)
 #pragma unroll 1
           for (int strand = 0; strand < S; ++strand) {
             float z[NV];
-            conv_gather_quads<C, NQW>(Tf, strand ? revcomp_window<M>(w) : w, q0, z);
-            if (BOTH) conv_gather_quads<C, NQW, true>(Tf, revcomp_window<M>(w), q0, z);
+            window_strand_z<C, NQW>(Tf, w, q0, strand, z);
             int at[NV];                // the counter of motif 4 q0 + j, -1: not this block's, or not resident
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
               const int kk = 4 * q0 + j, qq = q0 + j / 4;
               const float tb = (x_of_z(z[j]) - lo) * inv_w;
               const int bin = !(tb >= 0.f) ? 0 : tb >= nbf ? nb - 1 : (int)tb;
-              const bool live = kk >= kskip && kk < kend && qq >= g0 && qq < g1;
+              const bool live = kk >= span.kskip && kk < span.kend && qq >= g0 && qq < g1;
               at[j] = live ? ((kk - 4 * g0) * S + strand) * nb + bin : -1;
             }
             if (a.rotate) {
@@ -3172,11 +3181,11 @@ __device__ void scan_hist_body(const ScanHistArgs& a) {
       for (int i = threadIdx.x; i < per; i += blockDim.x) {
         uint32_t c = 0;
         for (int set = 0; set < a.copies; ++set) c += cnt[(size_t)set * per + i];
-        if (c) atomicAdd(a.hist + (size_t)(k0 + 4 * g0) * row + i, (unsigned long long)c);   // (counters of motifs past kend stay 0)
+        if (c) atomicAdd(a.hist + (size_t)(span.k0 + 4 * g0) * row + i, (unsigned long long)c);   // (counters of motifs past kend stay 0)
       }
       __syncthreads();
     }
-    if (threadIdx.x == 0 && y == 0 && *wcnt) atomicAdd(a.hist + (size_t)a.plan.K * row, (unsigned long long)*wcnt);
+    if (threadIdx.x == 0 && y == 0 && *wcnt) atomicAdd(a.hist + (size_t)in.plan.K * row, (unsigned long long)*wcnt);
   }
 }
 

@@ -8,10 +8,14 @@
 //   depth 1: set 0 only, every slab collected right after it has been enqueued.
 // A sweep of one slab uses set 0 only at either depth.  On the first error nothing more is enqueued or collected, drain()
 // is called once (the caller lets everything already enqueued run out there) and the error is returned; a sweep that
-// succeeds never calls drain().
+// succeeds never calls drain().  Below it: stream_plan, the segments a stream sweep hands to run_slabs.
 #pragma once
 
+#include <stddef.h>
+
 #include <algorithm>
+
+#include "crbm_layout.h"
 
 namespace crbm {
 
@@ -31,6 +35,28 @@ int run_slabs(int n, int slab, int depth, Enqueue enqueue, Collect collect, Drai
   if (!rc && pi >= 0) rc = collect(pi, pset, pstart, pcnt);
   if (rc) drain();
   return rc;
+}
+
+// The segments of a stream sweep (crbm_api.hip, StreamSweep): the T - M + 1 window starts of a stream of T >= M letters
+// go out `seg` at a time; segment [start, start + cnt) reads letters [start, start + cnt + M - 1), a halo of M - 1
+// behind its own.  A window start costs its staged byte, its letter and validity bits, per slab of the model its counts
+// and offsets, and a share of records: 4 + 4 nslab bytes of `budget` (CRBM_SLAB_BYTES, or 256 MB).  Unless the budget
+// was set by hand, a segment stays within 32 MB, so that a long stream has something to overlap.  Two buffer sets
+// exactly when there is more than one segment; `full` is the layout of a whole segment, what every set is sized for.
+struct StreamPlan {
+  int starts_all, seg, nsets;
+  ScanLayout full;
+};
+inline StreamPlan stream_plan(long T, int M, int nslab, size_t budget, bool budget_was_set) {
+  StreamPlan p;
+  p.starts_all = (int)(T - M + 1);
+  const size_t per_start = 4 + (size_t)4 * nslab;
+  size_t seg = std::max<size_t>(budget / per_start, 1);
+  if (!budget_was_set) seg = std::min(seg, std::max<size_t>(1, (32u << 20) / per_start));
+  p.seg = (int)std::min(seg, (size_t)p.starts_all);
+  p.nsets = p.seg < p.starts_all ? 2 : 1;
+  p.full = scan_layout((long)p.seg + M - 1, p.seg);
+  return p;
 }
 
 }  // namespace crbm

@@ -43,8 +43,8 @@ int emu_scan_tables(int id, const float* W, const float* b, const float* c, floa
 int emu_scan_run(int id, const float* tables, const unsigned char* codes, long T, float threshold, SiteRec* recs,
                  unsigned long long capacity, unsigned long long* count, uint32_t* flags, int grid, int threads,
                  unsigned long long* valid_out, uint32_t* letters_out) {
-  int M = 0, tab = 0;
-  SCAN_DISPATCH(id, (M = C::M, tab = C::TAB));
+  int M = 0, tab = 0, K = 0;
+  SCAN_DISPATCH(id, (M = C::M, tab = C::TAB, K = C::K));
   if (T < M) return -2;
   const long starts = T - M + 1;
   const ScanLayout l = scan_layout(T, starts);
@@ -60,14 +60,11 @@ int emu_scan_run(int id, const float* tables, const unsigned char* codes, long T
   emu::launch([&] { scan_encode_kernel(e); }, dim3(2), dim3(64), 0);
   if (valid_out) std::memcpy(valid_out, valid.data(), valid.size() * 8);
   if (letters_out) std::memcpy(letters_out, letters.data(), letters.size() * 4);
-  ScanArgs a;
-  a.tables = tables; a.letters = letters.data(); a.valid = valid.data();
+  ScanArgs a{ScanInput{tables, letters.data(), valid.data(), (int)starts, l.tiles, 0, SlabPlan{K, K, 0}}};
   a.lane_cnt = lanes.data(); a.tile_cnt = tiles.data(); a.tile_off = off.data();
   a.recs = recs; a.capacity = capacity;
-  a.starts = (int)starts; a.tiles = l.tiles; a.pos0 = 0; a.pass = 0; a.threshold = threshold;
-  a.table_stride = 0;
-  SCAN_DISPATCH(id, (a.plan.Ks = C::K, a.plan.K = C::K, a.plan.last_k0 = 0,
-                     emu::launch([&] { scan_sites_body<C>(a); }, dim3(grid), dim3(threads), (size_t)tab * 4)));
+  a.pos0 = 0; a.pass = 0; a.threshold = threshold; a.pad_ = 0;
+  SCAN_DISPATCH(id, emu::launch([&] { scan_sites_body<C>(a); }, dim3(grid), dim3(threads), (size_t)tab * 4));
   ScanOffsetsArgs o{tiles.data(), off.data(), off.data() + l.tiles, l.tiles};
   emu::launch([&] { scan_offsets_kernel(o); }, dim3(1), dim3(128), 128 * 8);
   *count = off[(size_t)l.tiles];

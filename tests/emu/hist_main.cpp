@@ -66,10 +66,10 @@ static int run(int K, long T, int nbins, int grid, int threads, int variant, int
     hp.lds = (long)C::TAB * 4 + 16L * S * nbins * gq + 4;
   }
   if (hp.gq < 1 || hp.lds > 160L * 1024) { fprintf(stderr, "no room for the counters\n"); return 2; }
-  ScanHistArgs a;
-  a.tables = tables.data(); a.letters = letters.data(); a.valid = valid.data(); a.hist = out->data() + GUARD;
-  a.starts = (int)starts; a.tiles = l.tiles; a.nbins = nbins; a.gq = hp.gq; a.copies = hp.copies; a.rotate = variant == 1;
-  a.lo = lo; a.inv_w = (float)nbins / (hi - lo); a.table_stride = C::TABLES_ALL; a.plan = plan;
+  ScanHistArgs a{ScanInput{tables.data(), letters.data(), valid.data(), (int)starts, l.tiles, C::TABLES_ALL, plan}};
+  a.hist = out->data() + GUARD;
+  a.nbins = nbins; a.gq = hp.gq; a.copies = hp.copies; a.rotate = variant == 1;
+  a.lo = lo; a.inv_w = (float)nbins / (hi - lo);
   emu::launch([&] { scan_hist_body<C>(a); }, dim3(grid, nslab), dim3(threads), (size_t)hp.lds);
   return 0;
 }

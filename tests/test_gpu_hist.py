@@ -2,7 +2,8 @@
 tests/hist_reference.py (exact row totals, tails inside the RTOL bands of the edges) on specialised and slabbed model
 classes of test_gpu_sweeps; the same bits for every CRBM_SLAB_BYTES and run; additivity over a gap and the windows a
 gap removes; a second binning; the use case (thresholds for a false-positive rate against scanSites' records, p-values);
-the refusals; and 2^22 letters on config #2's double-stranded model."""
+the refusals, a bad code in the first and in the last of several segments among them (scanSites too: the stream
+sweep's shared epilogue); and 2^22 letters on config #2's double-stranded model."""
 import ctypes
 
 import numpy as np
@@ -10,7 +11,7 @@ import pytest
 
 from tests.test_gpu_parity import make_pair, RTOL
 from tests.test_gpu_sweeps import CLASSES, ids, _model
-from tests.test_gpu_scan import gapped_stream, per_start
+from tests.test_gpu_scan import gapped_stream, per_start, _c_scan, _threshold, _same as _same_sites
 from tests.scan_reference import window_valid
 from tests.hist_reference import stream_logodds, check_histogram
 
@@ -156,6 +157,40 @@ def test_histogram_refusals_leave_the_handle_usable(monkeypatch):
     assert windows.value == 0 and not counts.ravel()[:10 * 2 * BINS].any() and np.all(counts.ravel()[10 * 2 * BINS:] == 77)
     none = m.scoreHistogram(np.full(200, 4, np.uint8), bins=BINS, lo=LO, hi=HI)
     assert none.windows == 0 and not none.counts.any()
+
+
+@pytest.mark.parametrize("cls", [CLASSES[0], CLASSES[2]], ids=ids([CLASSES[0], CLASSES[2]]))
+def test_a_bad_code_in_any_segment_is_refused_and_the_handle_stays_usable(cls, monkeypatch):
+    """(g) the epilogue both stream features share, over 7 segments on two streams (gapped_stream(5003, 2031)): a code
+    5 in the last segment, then in the first, makes crbm_scan_sites_codes and crbm_scan_histogram_codes (the C entry
+    points: the Python side would refuse first) fail with the "0..4" message, and after every refusal the same handle
+    returns, for the clean stream, records and counts equal bit for bit to those from before"""
+    from crbm_amd import _lib
+    name, K, M, ds, A, pool, Lf, L, env, spec = cls
+    m, o = _model(cls, monkeypatch)
+    stream = gapped_stream(T_A, SEED)
+    _, _, thr = _threshold(o, stream)
+    starts = T_A - M + 1
+    seg = starts // 7 + 1
+    assert -(-starts // seg) == 7
+    monkeypatch.setenv("CRBM_SLAB_BYTES", str(per_start(cls) * seg))
+    sites = m.scanSites(stream, thr)
+    hist = m.scoreHistogram(stream, bins=BINS, lo=LO, hi=HI)
+    assert sites.size > 0 and hist.windows > 0
+    counts = np.zeros((K, 2 if ds else 1, BINS), np.uint64)
+    windows = ctypes.c_int64(-1)
+    for p in (T_A - 2, 1):                       # read by the last segment alone; by the first alone
+        assert p >= 6 * seg + M - 1 or p < seg
+        bad = stream.copy()
+        bad[p] = 5
+        with pytest.raises(Exception, match=r"0\.\.4"):
+            _c_scan(m, bad, thr, sites.size)
+        _same_sites(sites, m.scanSites(stream, thr))
+        with pytest.raises(Exception, match=r"0\.\.4"):
+            m._call("crbm_scan_histogram_codes", bad.ctypes.data_as(_lib._U8P), bad.size, LO, HI, BINS,
+                    counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(windows))
+        _same(hist, m.scoreHistogram(stream, bins=BINS, lo=LO, hi=HI))
+        _same_sites(sites, m.scanSites(stream, thr))
 
 
 def test_histogram_scale_cfg2_two_to_the_22():

@@ -30,7 +30,7 @@ def gapped_stream(T, seed, share=0.01, run=25):
 
 
 def per_start(cls):
-    """bytes the driver counts per window start (crbm_api.hip, scan_sites_any): 4 + 4 per slab"""
+    """bytes the driver counts per window start (crbm_sweep.h, stream_plan): 4 + 4 per slab"""
     name, K, M, ds, A, pool, Lf, L, env, spec = cls
     return 4 + 4 * (1 if spec else -(-K // 60))
 
