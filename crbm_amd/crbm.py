@@ -19,6 +19,7 @@ import scipy.stats
 
 from . import _lib
 from ._lib import CrbmConfig, as_f32, fptr
+from .sequences import _LUT as _LETTER_LUT          # byte -> code 0..3 for ACGT / acgt, 255 otherwise
 
 
 _RAW_SITE = np.dtype([("seq", "<i4"), ("motif", "<i4"), ("start", "<i4"), ("strand", "<i4"), ("prob", "<f4")])   # crbm_site
@@ -605,6 +606,87 @@ class CRBM(object):
             counts += c.astype(np.int64)
             windows += w
         return ScoreHistogram(counts, np.linspace(lo, hi, int(bins) + 1), windows, self.doublestranded)
+
+    @staticmethod
+    def _letter_codes(x, what, V):
+        """`what` (alt or ref of variantEffects) as (V,) uint8 codes: a uint8 array of codes, or a string / an array of
+        letters ACGT (N and anything else: 255)"""
+        if isinstance(x, (str, bytes)):
+            x = np.frombuffer(x.encode("latin-1") if isinstance(x, str) else x, dtype=np.uint8)
+            codes = _LETTER_LUT[x]
+        else:
+            x = np.asarray(x)
+            if x.dtype == np.uint8:
+                codes = x
+            elif x.dtype.kind in "US" and x.dtype.itemsize == (4 if x.dtype.kind == "U" else 1):
+                flat = np.ascontiguousarray(x).view(np.uint32 if x.dtype.kind == "U" else np.uint8)
+                codes = _LETTER_LUT[np.minimum(flat, 255).astype(np.uint8)].reshape(x.shape)
+            else:
+                raise ValueError("%s must be a uint8 array of codes, or a string or an array of single letters ACGT" % what)
+        if codes.ndim != 1 or codes.size != V:
+            raise ValueError("%s must hold one entry per variant (%d), got shape %r" % (what, V, codes.shape))
+        return np.ascontiguousarray(codes)
+
+    def variantEffects(self, stream, pos, alt, offsets=None, seq=None, ref=None):
+        """What single-letter variants change in the model's free energy: dict of 'dfe' (V,) float32, 'per_motif' (V, K)
+        float32 and 'windows' (V,) int32.  dfe[i] = F(stream with letter pos[i] replaced by alt[i]) - F(stream), with F
+        the free energy of mutagenesis() taken over the valid windows of the stream (a window that touches a code 4 is
+        left out, as scanSites leaves it out); per_motif[i, k] is motif k's share of it (the hidden part only:
+        dfe = per_motif.sum(1) - (c[alt] - c[ref])), negative where the variant makes the motif fit better; windows[i]
+        counts the valid windows around the variant, 0..motif_length.  A variant on a code 4 gives zeros.
+        `stream` and `offsets` as in scanSites.  `pos`: integer positions in the stream, or -- with `offsets` and `seq`,
+        the record index of every variant -- positions inside record seq[i].  `alt`: a uint8 array of codes 0..3, or a
+        string or an array of letters ACGT.  `ref`, when given (codes or letters, N = 4), must be what the stream holds
+        at every position: the wrong-assembly check.  Variants may come in any order and may repeat; the outputs follow
+        the caller's order.  The same models are refused as in scanSites."""
+        _, stream, offsets = self._scan_input(stream, 0.0, offsets)
+        pos = np.asarray(pos)
+        if pos.ndim != 1 or not (np.issubdtype(pos.dtype, np.integer) or pos.size == 0):
+            raise ValueError("pos must be a 1-D integer array")
+        pos = pos.astype(np.int64)
+        V = pos.size
+        alt = self._letter_codes(alt, "alt", V)
+        if V and int(alt.max()) > 3:
+            raise ValueError("alt must hold letters: codes 0..3 or A, C, G, T")
+        if seq is not None:
+            if offsets is None:
+                raise ValueError("seq needs the offsets of the records")
+            seq = np.asarray(seq)
+            if seq.shape != pos.shape or not (np.issubdtype(seq.dtype, np.integer) or seq.size == 0):
+                raise ValueError("seq must be an integer array with one record index per variant")
+            seq = seq.astype(np.int64)
+            if V and (seq.min() < 0 or seq.max() >= offsets.size - 1):
+                raise ValueError("seq must lie in [0, %d)" % (offsets.size - 1))
+            length = offsets[seq + 1] - 1 - offsets[seq]
+            bad = np.flatnonzero((pos < 0) | (pos >= length))
+            if bad.size:
+                raise ValueError("pos outside its record at variants %s" % bad[:5].tolist())
+            pos = pos + offsets[seq]
+        bad = np.flatnonzero((pos < 0) | (pos >= stream.size))
+        if bad.size:
+            raise ValueError("pos outside the stream at variants %s" % bad[:5].tolist())
+        if ref is not None:
+            ref = self._letter_codes(ref, "ref", V)
+            ref = np.where(ref > 3, 4, ref).astype(np.uint8)
+            bad = np.flatnonzero(ref != stream[pos])
+            if bad.size:
+                raise ValueError("ref does not match the stream at %d of %d variants, the first at indices %s (another assembly?)"
+                                 % (bad.size, V, bad[:5].tolist()))
+        K = self.num_motifs
+        out = {"dfe": np.zeros(V, np.float32), "per_motif": np.zeros((V, K), np.float32), "windows": np.zeros(V, np.int32)}
+        for lo, hi in self._scan_cuts(stream, offsets):
+            idx = np.flatnonzero((pos >= lo) & (pos < hi))           # (a separator between two pieces holds no variant's letter: zeros)
+            if idx.size == 0:
+                continue
+            piece = stream[lo:hi]
+            p = np.ascontiguousarray(pos[idx] - lo)
+            a = np.ascontiguousarray(alt[idx])
+            dfe, pm, win = np.empty(idx.size, np.float32), np.empty((idx.size, K), np.float32), np.empty(idx.size, np.int32)
+            self._call("crbm_variant_effects_codes", piece.ctypes.data_as(_lib._U8P), piece.size, idx.size,
+                       p.ctypes.data_as(_lib._I64P), a.ctypes.data_as(_lib._U8P), fptr(dfe), fptr(pm),
+                       win.ctypes.data_as(_lib._I32P))
+            out["dfe"][idx], out["per_motif"][idx], out["windows"][idx] = dfe, pm, win
+        return out
 
     def motifBestSites(self, data):
         """The best site of every (sequence, motif): dict of 'start' (n,K) int32, 'strand' (n,K) int8 and

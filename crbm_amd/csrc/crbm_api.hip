@@ -173,6 +173,7 @@ struct crbm_handle {
     DevBuf<unsigned long long> scan_valid, scan_off;
     DevBuf<unsigned short> scan_lanes;
     DevBuf<uint32_t> scan_tiles;
+    DevBuf<int32_t> var_windows;                     // variant effects: the valid windows of a chunk's variants
   } set_bufs[2];
   int mut_route = 0;                               // route of the last crbm_mutagenesis* call: 1 fused kernel, 2 general path
   // annealed importance sampling (crbm_ais): the ladder, cA, the runs' log weights and letter codes between launches
@@ -1745,7 +1746,7 @@ int crbm_destroy(crbm_handle* h) {
   for (auto& b : h->set_bufs) {
     b.site_recs.release(); b.site_count.release(); b.site_keys.release();
     b.scan_valid.release(); b.scan_off.release(); b.scan_lanes.release(); b.scan_tiles.release();
-    b.mut_df.release(); b.mut_pll.release(); b.mut_rows.release();
+    b.mut_df.release(); b.mut_pll.release(); b.mut_rows.release(); b.var_windows.release();
   }
   h->ais_betas.release(); h->ais_base.release(); h->ais_logw.release(); h->ais_state.release(); h->hist.release();
   if (h->jk.module) (void)hipModuleUnload(h->jk.module);
@@ -2702,6 +2703,127 @@ int scan_hist_any(crbm_handle* h, const uint8_t* codes, int64_t T, float lo, flo
   return CRBM_OK;
 }
 
+// ---- variant effects (crbm_variant_effects_codes) -------------------------------------------------------------------
+// A two-stream sweep over the variant list in chunks (crbm_sweep.h, variant_plan).  Everything that can be refused is
+// refused on the host before anything is launched: outputs are then left as they were.  Per chunk, on its set's
+// stream: the host gathers the contexts (crbm_sweep.h, gather_contexts) and the alt bytes into the set's host buffer,
+// one copy takes them up; scan_encode_kernel makes letters and validity plane of the contexts,
+// crbm_variant_effects leaves per_motif [cnt][K] (set.oa) and the valid windows, variant_combine_kernel forms dfe
+// (set.ob); the outputs asked for are copied straight into the caller's arrays at the chunk's offset.  Every set owns
+// what it writes, sized for a whole chunk before the sweep starts.  CRBM_VARIANT_TIMING=1: tools/bench_variants.py.
+int variant_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t nvar, const int64_t* pos, const uint8_t* alt,
+                        float* dfe, float* per_motif, int32_t* windows) {
+  StreamSweep sw{h, "crbm_variant_effects_codes"};
+  int rc = sw.admit(codes, T);
+  if (rc) return rc;
+  ARGCHK(dfe || per_motif || windows, "null argument: at least one output is required");
+  ARGCHK(nvar >= 0 && nvar <= (int64_t)INT32_MAX, "nvar must lie in [0, 2^31 - 1]");
+  if (nvar == 0) return CRBM_OK;
+  ARGCHK(pos && alt, "null argument");
+  {
+    unsigned bad = 0;
+    for (int64_t i = 0; i < T; ++i) bad |= codes[i] > 4 ? 1u : 0u;
+    ARGCHK(!bad, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
+    for (int64_t i = 0; i < nvar; ++i) bad |= (pos[i] < 0 || pos[i] >= T ? 1u : 0u) | (alt[i] > 3 ? 2u : 0u);
+    ARGCHK(!(bad & 1u), "crbm_variant_effects_codes: every pos must lie in [0, T)");
+    ARGCHK(!(bad & 2u), "crbm_variant_effects_codes: every alt must be a letter code 0..3");
+  }
+  rc = sweep_begin(h);
+  if (rc) return rc;
+  const int M = sw.M, K = h->K, nslab = sw.nslab;
+  const VariantPlan vp = variant_plan((long)nvar, M, K, (size_t)env_int("CRBM_SLAB_BYTES", 256 << 20),
+                                      getenv("CRBM_SLAB_BYTES") != nullptr);
+  const int CW = vp.CW;
+  auto ctx_bytes = [&](int cnt) { return ((size_t)cnt * CW + 3) & ~(size_t)3; };   // the alt bytes follow the contexts
+  std::vector<uint8_t> host[2];
+  for (int i = 0; i < vp.nsets; ++i) {                     // everything both streams write, at its size, before either starts
+    const SweepSet set = sweep_set(h, i);
+    host[i].resize(ctx_bytes(vp.chunk) + (size_t)vp.chunk);
+    HIPCHK(set.stage->ensure((host[i].size() + 3) / 4));
+    HIPCHK(set.letters->ensure((size_t)vp.full.letter_words));
+    HIPCHK(set.own->scan_valid.ensure((size_t)vp.full.valid_words));
+    HIPCHK(set.oa->ensure((size_t)vp.chunk * K));
+    HIPCHK(set.ob->ensure((size_t)vp.chunk));
+    HIPCHK(set.own->var_windows.ensure((size_t)vp.chunk));
+  }
+  const bool timing = env_int("CRBM_VARIANT_TIMING", 0) != 0;
+  struct Events {                        // destroyed on every way out
+    hipEvent_t e[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    ~Events() {
+      for (auto& set : e)
+        for (hipEvent_t ev : set)
+          if (ev) (void)hipEventDestroy(ev);
+    }
+  } events;
+  auto& tev = events.e;
+  double device_ms = 0.0;
+  int chunks = 0;
+  if (timing)
+    for (int i = 0; i < 2; ++i)
+      for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
+  rc = run_slabs((int)nvar, vp.chunk, 2,
+    [&](int, int si, int start, int cnt) -> int {
+      const SweepSet set = sweep_set(h, si);
+      uint8_t* ctx = host[si].data();
+      uint8_t* alts = ctx + ctx_bytes(cnt);
+      gather_contexts(codes, T, pos + start, cnt, M, ctx);
+      std::memcpy(alts, alt + start, (size_t)cnt);
+      const size_t up = ctx_bytes(cnt) + (size_t)cnt;
+      HIPCHK(hipMemcpyAsync(set.stage->p, ctx, up, hipMemcpyHostToDevice, set.st));
+      if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
+      const long n = (long)cnt * CW;
+      const ScanLayout l = scan_layout(n, cnt);
+      const unsigned char* staged = reinterpret_cast<const unsigned char*>(set.stage->p);
+      ScanEncodeArgs e;
+      e.codes = staged;
+      e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;   // (no code above 4: checked above)
+      e.n = n; e.valid_words = l.valid_words;
+      hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
+      HIPCHK(hipGetLastError());
+      VariantArgs a{};
+      a.tables = h->big() ? h->d_slab_tables : h->d_tables;
+      a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
+      a.starts = (int32_t)(n - M + 1); a.tiles = l.tiles; a.table_stride = sw.kms->TABLES_ALL;
+      if (h->big()) a.plan = slab_plan(h);
+      else { a.plan.Ks = K; a.plan.K = K; a.plan.last_k0 = 0; }
+      a.alt = staged + ctx_bytes(cnt);
+      a.per_motif = set.oa->p; a.windows = set.own->var_windows.p;
+      a.cnt = cnt; a.pad_ = 0;
+      const unsigned gx = (unsigned)std::max(1, std::min((l.tiles + 3) / 4, std::max(1, h->num_cu * 8 / nslab)));
+      HIPCHK(jit_launch(sw.kjk->variant_effects, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(*sw.kms), set.st));
+      if (dfe) {
+        VariantCombineArgs c;
+        c.per_motif = set.oa->p; c.codes = staged; c.alt = a.alt; c.c = h->dc; c.dfe = set.ob->p;
+        c.cnt = cnt; c.K = K; c.CW = CW; c.M = M;
+        hipLaunchKernelGGL(variant_combine_kernel, dim3(grid_for(cnt, 256, h->num_cu * 8)), dim3(256), 0, set.st, c);
+        HIPCHK(hipGetLastError());
+      }
+      if (timing) HIPCHK(hipEventRecord(tev[si][1], set.st));
+      return CRBM_OK;
+    },
+    [&](int, int si, int start, int cnt) -> int {
+      const SweepSet set = sweep_set(h, si);
+      const size_t at = (size_t)start;
+      if (dfe) HIPCHK(hipMemcpyAsync(dfe + at, set.ob->p, (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      if (per_motif) HIPCHK(hipMemcpyAsync(per_motif + at * K, set.oa->p, (size_t)cnt * K * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      if (windows) HIPCHK(hipMemcpyAsync(windows + at, set.own->var_windows.p, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, set.st));
+      HIPCHK(hipStreamSynchronize(set.st));
+      if (timing) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, tev[si][0], tev[si][1]));
+        device_ms += ms;
+        ++chunks;
+      }
+      return CRBM_OK;
+    },
+    [&] { sweep_drain(h); });
+  if (rc) return rc;
+  if (timing) fprintf(stderr, "crbm_variant_effects_codes: kernels %.3f ms over %d chunks\n", device_ms, chunks);
+  HIPCHK(hipStreamSynchronize(h->stream2));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return CRBM_OK;
+}
+
 // ---- in-silico mutagenesis (crbm_mutagenesis*) ----------------------------------------------------------------------
 // dF (n,L,A) and / or pll (n) over a source, a two-stream sweep.  Specialised models without pooling: the fused
 // crbm_mutagenesis pass (mutagenesis_body; as many waves per block as the LDS holds accumulators beside the tables).
@@ -2956,6 +3078,12 @@ int crbm_scan_histogram_codes(crbm_handle* h, const uint8_t* codes, int64_t T, f
                               uint64_t* counts, int64_t* windows) {
   ENTER();
   return scan_hist_any(h, codes, T, lo, hi, nbins, counts, windows);
+}
+
+int crbm_variant_effects_codes(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t nvar, const int64_t* pos,
+                               const uint8_t* alt, float* dfe, float* dfe_per_motif, int32_t* windows) {
+  ENTER();
+  return variant_effects_any(h, codes, T, nvar, pos, alt, dfe, dfe_per_motif, windows);
 }
 
 int crbm_mutagenesis(crbm_handle* h, const float* v, int32_t n, int32_t L, float* dfe, float* pll) {

@@ -3189,6 +3189,103 @@ __device__ void scan_hist_body(const ScanHistArgs& a) {
   }
 }
 
+// ===========================================================================
+// Variant effects (crbm_variant_effects_codes): what one substitution changes in the free energy of a stream, per motif.
+// The host gathers the context [pos - M + 1, pos + M - 1] of every variant of a chunk, CW = 2M - 1 codes with 4 for the
+// positions outside the stream; the contexts back to back are a stream of cnt * CW codes that scan_encode_kernel turns
+// into the letters and the validity plane of scan_layout.  The windows that cover variant v's letter start at
+// s = v * CW + m, m in [0, M), and none of them reaches into a neighbour's context: a variant sees its own context alone.
+// A wave owns a tile of 64 variants, a lane one of them.  The lane walks its M windows in ascending m, + strand before
+// -, for NQW motif quads at a time (the outer loop): z of the window as free_energy_body gathers it (conv_gather_quads
+// per strand, strand <= DS -- NOT window_strand_z's site score), then mutagenesis_body's one other table row: the
+// variant's letter sits at offset o = strand ? m : M - 1 - m of the strand's window, in group g = o / G at slot t, and
+// T[g][r ^ (x << 2t)] - T[g][r] with x = ref ^ alt is what the substitution adds to z (complementing commutes with
+// ^ x: the same x on both strands).  m, g and t are wave-uniform; x and the rows differ between lanes.  The differences
+// softplus(z_alt) - softplus(z_ref) of the valid windows are subtracted from the lane's registers acc[] (F carries
+// -softplus) in that fixed order and stored to per_motif [cnt][K]: no cross-lane sum, no atomics, no LDS accumulator --
+// a variant's bits depend on its context alone, not on the chunk, its place in the list or the launch geometry.
+// alt == ref: x = 0, the same row twice, exactly 0.  ref no letter: no window is valid, all 0.
+// blockIdx.y is the slab of a generic DNA model, which writes its own columns [k0 + kskip, k0 + kend); slab 0 counts the
+// valid windows.  variant_combine_kernel (below, model-independent) sums a row in ascending k and adds the bias term.
+// ===========================================================================
+struct VariantArgs : ScanInput {         // starts = cnt * CW - M + 1 (unused), tiles = tiles of 64 VARIANTS
+  const unsigned char* alt;              // [cnt] codes 0..3
+  float* per_motif;                      // [cnt][K]
+  int32_t* windows;                      // [cnt]
+  int32_t cnt;
+  int32_t pad_;
+};
+
+template <class C>
+__device__ void variant_effects_body(const VariantArgs& a) {
+  if constexpr (C::POOL == 1) {       // refused on the host, as the scan
+    constexpr int K = C::K, M = C::M, G = C::G, CW = 2 * M - 1;
+    constexpr int NQW = C::NQ < 4 ? C::NQ : 4, NV = 4 * NQW;
+    HIP_DYNAMIC_SHARED(float, smem);
+    float* Tf = smem;
+    const ScanInput& in = a;
+    const int y = (int)blockIdx.y;
+    const SlabSpan span = slab_span<C>(in.plan, y);
+    copy_tables<C::TAB>(Tf, in.tables + (size_t)y * in.table_stride + C::OFF_TF);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    for (int t = blockIdx.x * nwaves + wave; t < in.tiles; t += gridDim.x * nwaves) {
+      const int v = 64 * t + lane;
+      const bool live = v < a.cnt;
+      const int base = (live ? v : a.cnt - 1) * CW;          // (idle lanes of the last tile repeat its last variant)
+      const int p = base + M - 1;                            // the variant's own position: letter 0 under a code 4, where
+      const uint32_t ref = (in.letters[p >> 4] >> (2 * (p & 15))) & 3u;   // no window is valid and x does not matter
+      const uint32_t x = ref ^ (uint32_t)(a.alt[live ? v : a.cnt - 1] & 3u);
+      int nwin = 0;
+#pragma unroll 1
+      for (int q0 = 0; q0 < C::NQ; q0 += NQW) {
+        float acc[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) acc[j] = 0.f;
+#pragma unroll 1
+        for (int m = 0; m < M; ++m) {
+          const int s = base + m;
+          const bool ok = window_valid<M>(in.valid, s);
+          if (q0 == 0) nwin += ok ? 1 : 0;
+          const LetterWin<M> fwd = letter_window<M>(in.letters, s);
+#pragma unroll 1
+          for (int strand = 0; strand <= C::DS; ++strand) {
+            const LetterWin<M> win = strand ? revcomp_window<M>(fwd) : fwd;
+            float z[NV];
+            conv_gather_quads<C, NQW>(Tf, win, q0, z);
+            const int o = strand ? m : M - 1 - m;            // the variant's letter in this strand's window
+            const int g = o / G, tt = o - g * G;
+            const uint32_t r = window_bits<M>(win, 2 * G * g) & (uint32_t)(C::ROWS - 1);
+            const uint32_t r2 = r ^ (x << (2 * tt));
+            const float4* tab = reinterpret_cast<const float4*>(Tf + (size_t)g * C::ROWS * C::KP) + q0;
+#pragma unroll
+            for (int q = 0; q < NQW; ++q)
+              if (q0 + q < C::NQ) {                          // wave-uniform
+                const float4 cv = tab[(size_t)r * C::NQ + q], av = tab[(size_t)r2 * C::NQ + q];
+                const float cur[4] = {cv.x, cv.y, cv.z, cv.w}, alt[4] = {av.x, av.y, av.z, av.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                  if (4 * (q0 + q) + e < K) {
+                    const float d = softplus_of_z(z[4 * q + e] + (alt[e] - cur[e])) - softplus_of_z(z[4 * q + e]);
+                    if (ok) acc[4 * q + e] -= d;
+                  }
+              }
+          }
+        }
+        if (live) {
+          float* out = a.per_motif + (size_t)v * in.plan.K + span.k0;
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            const int kk = 4 * q0 + j;
+            if (kk >= span.kskip && kk < span.kend) out[kk] = acc[j];
+          }
+        }
+      }
+      if (live && y == 0) a.windows[v] = nwin;
+    }
+  }
+}
+
 #ifdef CRBM_DEFINE_MISC_KERNELS
 // ===========================================================================
 // Model-independent kernels, compiled ahead of time into libcrbm_hip.so.
@@ -3394,6 +3491,27 @@ __global__ void __launch_bounds__(1024) scan_offsets_kernel(ScanOffsetsArgs a) {
     at += cnt[i];
   }
   if (tid == nt - 1) a.total[blockIdx.x] = part[tid];
+}
+
+// The tail of the variant effects (variant_effects_body): dfe[i] = sum_k per_motif[i][k] - (c[alt_i] - c[ref_i]), the
+// motifs added in ascending k -- one rule for a model on its own kernels and for one that runs as slabs -- and exactly 0
+// where the variant sits on no letter (its row is all zeros then).  ref_i is code M - 1 of the staged context.
+struct VariantCombineArgs {
+  const float* per_motif;       // [cnt][K]
+  const unsigned char* codes;   // [cnt][CW], the staged contexts
+  const unsigned char* alt;     // [cnt]
+  const float* c;               // (4) the visible bias
+  float* dfe;                   // [cnt]
+  int32_t cnt, K, CW, M;
+};
+__global__ void __launch_bounds__(256) variant_combine_kernel(VariantCombineArgs a) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.cnt; i += gridDim.x * blockDim.x) {
+    const uint32_t ref = a.codes[(size_t)i * a.CW + a.M - 1];
+    const float* row = a.per_motif + (size_t)i * a.K;
+    float s = 0.f;
+    for (int k = 0; k < a.K; ++k) s += row[k];
+    a.dfe[i] = ref < 4u ? s - (a.c[a.alt[i] & 3u] - a.c[ref]) : 0.f;
+  }
 }
 
 // packed letters -> one-hot fp32 (n,1,4,L)

@@ -12,6 +12,8 @@
 #pragma once
 
 #include <stddef.h>
+#include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 
@@ -57,6 +59,41 @@ inline StreamPlan stream_plan(long T, int M, int nslab, size_t budget, bool budg
   p.nsets = p.seg < p.starts_all ? 2 : 1;
   p.full = scan_layout((long)p.seg + M - 1, p.seg);
   return p;
+}
+
+// The chunks of a variant sweep (crbm_api.hip, variant_effects_any): nvar >= 1 variants go out `chunk` at a time.  A
+// variant costs its staged context of CW = 2M - 1 bytes, their letter and validity bits (3 bits each), the outputs
+// 4 (K + 2) and its alt byte out of `budget` (CRBM_SLAB_BYTES, or 256 MB); unless the budget was set by hand a chunk
+// stays within 32 MB, so that a long list has something to overlap.  A chunk's contexts are one stream for the kernels,
+// whose window starts are 32 bits wide: chunk * CW stays within 2^30.  Two buffer sets exactly when there is more than
+// one chunk; `full` is the layout of a whole chunk, what every set is sized for.
+struct VariantPlan {
+  int chunk, nsets, CW;
+  size_t per_variant;
+  ScanLayout full;
+};
+inline VariantPlan variant_plan(long nvar, int M, int K, size_t budget, bool budget_was_set) {
+  VariantPlan p;
+  p.CW = 2 * M - 1;
+  p.per_variant = (size_t)p.CW + ((size_t)3 * p.CW + 7) / 8 + (size_t)4 * (K + 2) + 1;
+  size_t chunk = std::max<size_t>(budget / p.per_variant, 1);
+  if (!budget_was_set) chunk = std::min(chunk, std::max<size_t>(1, (32u << 20) / p.per_variant));
+  chunk = std::min(chunk, ((size_t)1 << 30) / (size_t)p.CW);
+  p.chunk = (int)std::min(chunk, (size_t)nvar);
+  p.nsets = p.chunk < nvar ? 2 : 1;
+  p.full = scan_layout((long)p.chunk * p.CW, p.chunk);      // (tiles: of 64 variants)
+  return p;
+}
+// the contexts of variants pos[0 .. cnt) of a stream of T codes, CW = 2M - 1 bytes each at dst: codes
+// [pos - M + 1, pos + M - 1], code 4 (no letter) for what lies outside the stream; every pos inside [0, T)
+inline void gather_contexts(const uint8_t* codes, int64_t T, const int64_t* pos, int cnt, int M, uint8_t* dst) {
+  const int CW = 2 * M - 1;
+  for (int i = 0; i < cnt; ++i, dst += CW) {
+    const int64_t lo = pos[i] - (M - 1);
+    if (lo >= 0 && lo + CW <= T) memcpy(dst, codes + lo, (size_t)CW);
+    else
+      for (int j = 0; j < CW; ++j) dst[j] = lo + j >= 0 && lo + j < T ? codes[lo + j] : (uint8_t)4;
+  }
 }
 
 }  // namespace crbm

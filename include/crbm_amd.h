@@ -262,6 +262,34 @@ int crbm_scan_sites_codes(crbm_handle* h, const uint8_t* codes, int64_t T, float
 int crbm_scan_histogram_codes(crbm_handle* h, const uint8_t* codes, int64_t T, float lo, float hi, int32_t nbins,
                               uint64_t* counts, int64_t* windows);
 
+/* ---- variant effects: what a substitution changes in the free energy of a stream ---
+ * Given a stream and a list of variants (position, alternative letter): how much does each variant change the model's
+ * free energy, and which motif gains or loses the site.  Stream, codes and window validity as crbm_scan_sites_codes:
+ * codes 0..3 are letters, 4 is no letter, a window [s, s+M) is valid when all M codes are letters.  The free energy
+ * of a stream is
+ *   F(stream) = - sum_{valid windows s, strands, motifs k} softplus(x_{k,strand}(s)) - sum_{letters p} c[v_p],
+ * the stream form of the F that crbm_mutagenesis documents: the hidden terms are those of crbm_free_energy (the
+ * activation of each strand of a double-stranded model, the forward strand alone of a single-stranded one) -- not the
+ * site score of the scan, which for single-stranded models adds both orientations.
+ * For variant i = (pos_i, alt_i) with ref = codes[pos_i]:
+ *   dfe_per_motif[i,k] = - sum over the valid windows s in [pos_i-M+1, pos_i] within [0, T-M] and the strands of
+ *                          softplus(x_alt) - softplus(x_ref) for motif k: the hidden part only       (nvar,K) fp32
+ *   dfe[i]             = sum_k dfe_per_motif[i,k] - (c[alt_i] - c[ref]), the motifs added in ascending k   (nvar) fp32
+ *   windows[i]         = the number of valid windows that entered, 0..M                                  (nvar) int32
+ * alt == ref gives exactly 0 everywhere.  ref == 4 (the variant sits on an N or a separator) gives windows = 0,
+ * dfe = 0 and dfe_per_motif = 0.  A letter with no valid window around it (T < M, or gaps on both sides) gives
+ * windows = 0 and dfe equal to the bias term alone.  A window that touches a gap elsewhere is left out, as the scan
+ * leaves it out.  Every output of a variant depends on that variant and the stream alone: the same bits in every
+ * run, for every CRBM_SLAB_BYTES (the list goes through the device in chunks, 2M - 1 context bytes per variant),
+ * for every launch geometry and under any permutation or duplication of the list.  Variants may come in any order
+ * and may repeat.  Any of the three outputs may be NULL; nvar == 0 succeeds and writes nothing.
+ * Served: exactly the models crbm_scan_sites_codes serves.
+ * CRBM_ERR_INVALID: pooling > 1, another alphabet, a generic-only model; all three outputs NULL; nvar < 0 or
+ * > 2^31 - 1, a pos outside [0, T), an alt > 3, a code above 4, T < 0, T > 2^31 - 1 -- all found on the host before
+ * anything is launched: the outputs are left as they were.  The handle stays usable after a refusal. */
+int crbm_variant_effects_codes(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t nvar, const int64_t* pos,
+                               const uint8_t* alt, float* dfe, float* dfe_per_motif, int32_t* windows);
+
 /* ---- in-silico mutagenesis and pseudo-log-likelihood -----------------------------
  * WHICH bases matter.  With F(v) = L * crbm_free_energy(v), the unnormalised free energy of one sequence (derived from
  * theano_freeEnergyForData, convRBM.py:657-676: the hidden terms of all motifs and strands, pooled form when
