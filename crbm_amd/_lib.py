@@ -140,6 +140,7 @@ SIGNATURES = {
     "crbm_get_launch_info": (_I32, [_H, ctypes.POINTER(CrbmLaunchInfo)]),
     "crbm_copy_bandwidth": (_I32, [_H, ctypes.c_int64, _I32, _F]),
     "crbm_last_shader_clock": (_I32, [_H, _F]),
+    "crbm_geometry_launches": (_I32, [_H, _I64P, _I64P]),
     "crbm_gibbs_state_bytes": (ctypes.c_int64, [_H]),
 }
 

@@ -84,7 +84,11 @@ def prune_cache(verbose=True):
 def precompile(configs, verbose=True):
     """JIT-compile the kernels of the given models into the on-disk cache.
     configs: iterable of dicts with num_motifs, motif_length, doublestranded,
-    batchsize, fantasy_hidden_len.  Needs no GPU."""
+    batchsize, fantasy_hidden_len.  Besides the model's kernels this compiles the chain
+    kernels of the launch geometry of that batchsize and fantasy_hidden_len where the
+    plan has them (crbm_plan.h, LaunchPlan::geo_plain / geo_fused).  An optional "env"
+    dict holds plan knobs (CRBM_GEOM, CRBM_GIBBS_S, ...) set while that entry is
+    compiled.  Needs no GPU."""
     import ctypes
     sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
     from crbm_amd import _lib
@@ -94,7 +98,17 @@ def precompile(configs, verbose=True):
                               doublestranded=int(c.get("doublestranded", 0)), batchsize=c.get("batchsize", 20),
                               cd_k=1, pooling=c.get("pooling", 1), fantasy_hidden_len=c.get("fantasy_hidden_len", 200),
                               learning_rate=0.1, momentum=0.9, rho=0.01, lambda_rate=0.1, seed=0, device=0, reserved=0)
-        rc = lib.crbm_precompile(ctypes.byref(cfg))
+        knobs = c.get("env", {})
+        saved = {k: os.environ.get(k) for k in knobs}
+        os.environ.update(knobs)
+        try:
+            rc = lib.crbm_precompile(ctypes.byref(cfg))
+        finally:
+            for k, v in saved.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
         if rc != 0:
             raise RuntimeError("precompile failed for %s: %s" % (c, lib.crbm_last_error(None).decode()))
         if verbose:

@@ -226,6 +226,8 @@ struct crbm_handle {
   unsigned long long* d_probe = nullptr;   // {wall ticks, shader cycles, scratch, scratch} summed over the launches of all crbm_time_gibbs calls
   unsigned long long probe_base[2] = {0, 0}, probe_last[2] = {0, 0};   // the sums before / after the last call
   bool probe_on = false;
+  JitGeoKernels jg;             // the chain kernels compiled for the plan's launch shapes (LaunchPlan::geo_plain / geo_fused)
+  long long geo_launches[2] = {0, 0};   // chain kernel launches in the run-time form, with the geometry compiled in (crbm_geometry_launches)
   unsigned long long* d_timeline = nullptr;   // CRBM_GIBBS_TIMELINE: first / last tick of block 0 of every launch of a crbm_time_gibbs call
   int timeline_cap = 0, timeline_next = 0;
   unsigned long long ipc_timeout_ticks = 0;   // bound of an update launch's wait for its peers, in ticks of the GPU's wall clock
@@ -499,6 +501,21 @@ StatsGeom stats_geom(const StatsMfmaLayout& st, float* partials, long ngroups, i
 // launch also leaves the model half of the gradient statistics as one partial row per block in
 // h->partials2 (sized here: all this writes to the handle) and the column reduction is handed back
 // through `model_reduce`.  The caller that launches sets h->nset_slots.
+JitGeo jit_geo(const GeoSpec& s, int Lf) {
+  JitGeo j;
+  if (!s.on()) return j;
+  j.S = s.gl.S; j.Lf = Lf; j.Lv = s.gl.Lv; j.Lrow = s.gl.Lrow; j.LWs = s.gl.LWs; j.nvb = s.gl.nvb; j.nhb = s.gl.nhb;
+  j.threads = s.threads; j.nchains = s.nchains; j.grid = s.grid; j.aligned = s.aligned ? 1 : 0; j.group = s.group;
+  return j;
+}
+
+// The kernel compiled for exactly this launch (GeoSpec), or null: then the launch takes the run-time form.  Launches
+// without steps and launches with profiling aids (debug, timeline) are the run-time form's.
+hipFunction_t geo_kernel(const GeoSpec& spec, hipFunction_t fn, const ChainGeom& g, const GibbsArgs& a) {
+  if (!fn || a.steps < 1 || a.debug || a.timeline) return nullptr;
+  return spec.serves(g.gl, g.threads, a.nblocks, a.nchains) && a.Lf == spec.gl.nhb ? fn : nullptr;
+}
+
 int prepare_gibbs(crbm_handle* h, const ChainGeom& g, int steps, ReduceArgs* model_reduce, GibbsArgs* out, unsigned* lds_out) {
   const GibbsLayout& gl = g.gl;
   GibbsArgs& a = *out;
@@ -643,18 +660,21 @@ int launch_gibbs_parts(crbm_handle* h, int steps) {
     if (p > 0) ap.clock = nullptr;
     if (h->d_timeline && h->timeline_next < h->timeline_cap) ap.timeline = h->d_timeline + 2 * (size_t)(h->timeline_next++);
     ap.nblocks = (int)grid;
+    hipFunction_t fn = geo_kernel(plan.geo_plain, h->jg.gibbs_sparse, plan.part, ap);
+    h->geo_launches[fn ? 1 : 0] += 1;
+    if (!fn) fn = h->jk.gibbs_sparse;
     if (p > 0) {          // the partition's own thread enqueues it
       PartWorker* w = h->part_worker[p];
       {
         std::lock_guard<std::mutex> lock(w->mu);
-        w->jobs.push_back(PartJob{h->jk.gibbs_sparse, ap, grid, threads, lds, (unsigned long long)(stagger_ticks * p)});
+        w->jobs.push_back(PartJob{fn, ap, grid, threads, lds, (unsigned long long)(stagger_ticks * p)});
       }
       w->cv.notify_one();
       continue;
     }
     const bool calibrate = first_of_fork && !h->cal_pending;
     if (calibrate) HIPCHK(hipEventRecord(h->ev_cal0, h->part_stream[0]));
-    HIPCHK(jit_launch(h->jk.gibbs_sparse, ap, grid, 1, threads, lds, h->part_stream[0]));
+    HIPCHK(jit_launch(fn, ap, grid, 1, threads, lds, h->part_stream[0]));
     if (calibrate) {
       HIPCHK(hipEventRecord(h->ev_cal1, h->part_stream[0]));
       h->cal_pending = true;
@@ -686,6 +706,12 @@ int launch_gibbs(crbm_handle* h, int steps, hipStream_t s = nullptr, ReduceArgs*
   h->nset_slots = g.grid * (g.threads / 64);
   if (plain && h->d_timeline && h->timeline_next < h->timeline_cap) a.timeline = h->d_timeline + 2 * (size_t)(h->timeline_next++);
   hipFunction_t fn = model_reduce ? h->jk.gibbs_sparse_stats : (h->variant ? h->jk.gibbs_sparse : h->jk.gibbs);
+  if (h->variant == 1) {
+    hipFunction_t geo = model_reduce ? geo_kernel(h->plan.geo_fused, h->jg.gibbs_sparse_stats, g, a)
+                                     : geo_kernel(h->plan.geo_plain, h->jg.gibbs_sparse, g, a);
+    if (geo) fn = geo;
+    h->geo_launches[geo ? 1 : 0] += 1;
+  }
   HIPCHK(jit_launch(fn, a, (unsigned)g.grid, 1, (unsigned)g.threads, lds, s));
   h->gibbs_step += (uint32_t)steps;
   h->launches_since_read += 1;
@@ -1085,7 +1111,9 @@ int train_local_dev(crbm_handle* h, const uint32_t* d_letters, int n, int L, boo
     t.g.sg.lds_floats = (int)(lds / 4);
     t.d.sg.lds_floats = (int)(lds / 4);
     h->nset_slots = g.grid * (g.threads / 64);
-    HIPCHK(jit_launch(h->jk.train_local, t, (unsigned)(g.grid + d.grid), 1, (unsigned)g.threads, lds, h->stream));
+    hipFunction_t fn = h->variant == 1 ? geo_kernel(h->plan.geo_fused, h->jg.train_local, g, t.g) : nullptr;
+    h->geo_launches[fn ? 1 : 0] += 1;
+    HIPCHK(jit_launch(fn ? fn : h->jk.train_local, t, (unsigned)(g.grid + d.grid), 1, (unsigned)g.threads, lds, h->stream));
     h->gibbs_step += (uint32_t)h->cfg.cd_k;
     h->launches_since_read += 1;
     return launch_reduce_pair(h, pair, publish);
@@ -1563,6 +1591,10 @@ int crbm_precompile(const crbm_config* cfg) {
     rc_jit = jit_compile(p.ms.K, p.ms.M, p.ms.DS, p.G, p.GS, p.ms.POOL, p.gibbs_wpe, p.gibbs_tb, &code, &cached, &file, &err);
   else if (p.slab_K > 0)      // the generic kernels are compiled ahead of time; the kernels of the model's slab model are specialised
     rc_jit = jit_compile(p.slab_K, p.ms.M, p.ms.DS, p.slab_G, p.slab_G, p.slab_ms.POOL, 0, 256, &code, &cached, &file, &err, true);
+  if (rc_jit == 0 && !p.big && (p.geo_plain.on() || p.geo_fused.on())) {
+    const int Lf = cfg->fantasy_hidden_len > 0 ? cfg->fantasy_hidden_len : 200;
+    rc_jit = jit_compile_geo(p.ms.K, p.ms.M, p.ms.DS, p.ms.POOL, p.gibbs_wpe, jit_geo(p.geo_plain, Lf), jit_geo(p.geo_fused, Lf), &code, &cached, &file, &err);
+  }
   if (rc_jit != 0) {
     g_create_error = err;
     return CRBM_ERR_HIP;
@@ -1627,6 +1659,12 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
     std::string err;
     if (jit_load(hh->K, hh->M, hh->ds, plan.G, plan.GS, hh->ms().POOL, plan.gibbs_wpe, plan.gibbs_tb, &hh->jk, &err) != 0) {
       g_create_error = "kernel specialisation failed: " + err;
+      return bail(CRBM_ERR_HIP);
+    }
+    // (only the set-bit walk has them: a handle pinned to the dense variant never consults jg and does not pay for it)
+    if (hh->variant == 1 &&
+        jit_load_geo(hh->K, hh->M, hh->ds, hh->ms().POOL, plan.gibbs_wpe, jit_geo(plan.geo_plain, hh->Lf), jit_geo(plan.geo_fused, hh->Lf), &hh->jg, &err) != 0) {
+      g_create_error = "kernel specialisation (launch geometry) failed: " + err;
       return bail(CRBM_ERR_HIP);
     }
   }
@@ -1750,6 +1788,7 @@ int crbm_destroy(crbm_handle* h) {
   }
   h->ais_betas.release(); h->ais_base.release(); h->ais_logw.release(); h->ais_state.release(); h->hist.release();
   if (h->jk.module) (void)hipModuleUnload(h->jk.module);
+  if (h->jg.module) (void)hipModuleUnload(h->jg.module);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -3438,6 +3477,13 @@ int crbm_copy_bandwidth(crbm_handle* h, int64_t bytes, int32_t reps, float* gb_p
   (void)hipFree(src); (void)hipFree(dst);
   if (e != hipSuccess) return fail(h, CRBM_ERR_HIP, std::string("copy bandwidth: ") + hipGetErrorString(e));
   *gb_per_s = (float)(2.0 * (double)n4 * 16.0 * reps / (ms * 1e-3) / 1e9);   // bytes read + written
+  return CRBM_OK;
+}
+
+int crbm_geometry_launches(const crbm_handle* h, int64_t* compiled_in, int64_t* run_time) {
+  if (!h) return CRBM_ERR_INVALID;
+  if (compiled_in) *compiled_in = h->geo_launches[1];
+  if (run_time) *run_time = h->geo_launches[0];
   return CRBM_OK;
 }
 

@@ -121,16 +121,67 @@ inline std::string jit_stub(int K, int M, int DS, int G, int GS, int POOL, int g
   return buf;
 }
 
+// One launch shape of the geometry-specialised chain kernels (crbm_plan.h, GeoSpec), as the stub needs it
+struct JitGeo {
+  int S = 0, Lf = 0, Lv = 0, Lrow = 0, LWs = 0, nvb = 0, nhb = 0, threads = 0, nchains = 0, grid = 0, aligned = 0, group = 0;
+  bool on() const { return threads > 0; }
+};
+
+// The chain kernels of a model with the launch geometry compiled in (crbm_kernels.h, GeomCT): a code object of its own
+// beside the model's, keyed by the same source text and by the geometry constants, so that handles of the same model
+// with other chain counts keep sharing the model's module.  plain: crbm_gibbs_sparse_geo; fused: the chain launch with
+// statistics and the fused training launch (crbm_gibbs_sparse_stats_geo, crbm_train_local_geo).
+// Only the plain kernel samples the clocks (GibbsArgs::clock, in gibbs_geo_body around the body); the two fused kernels
+// ignore it: the host sets `clock` in crbm_time_gibbs alone, whose launches are plain ones.  A caller that ever times
+// fused launches with it has to send them to the run-time form (geo_kernel in crbm_api.hip).
+inline std::string jit_geo_stub(int K, int M, int DS, int POOL, int gibbs_wpe, const JitGeo& plain, const JitGeo& fused) {
+  char attr[96];
+  if (gibbs_wpe > 0) snprintf(attr, sizeof(attr), "__attribute__((amdgpu_waves_per_eu(1, %d)))", gibbs_wpe);
+  else snprintf(attr, sizeof(attr), "__attribute__((amdgpu_waves_per_eu(4)))");
+  std::string s = "#define CRBM_SLAB_KERNELS 0\n#include \"crbm_kernels.h\"\n#ifndef CRBM_GIBBS_ATTR\n#define CRBM_GIBBS_ATTR ";
+  s += attr;
+  s += "\n#endif\n";
+  char buf[1024];
+  auto policy = [&](const char* name, const char* cfg, const JitGeo& g) {
+    snprintf(buf, sizeof(buf), "using %s = crbm::Cfg<%d, %d, %d, %d, %d>;\nusing %sGeo = crbm::GeomCT<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %s>;\n",
+             cfg, K, M, DS, g.group, POOL, name, g.S, g.Lf, g.Lv, g.Lrow, g.LWs, g.nvb, g.nhb, g.threads, g.nchains, g.grid, g.aligned ? "true" : "false");
+    s += buf;
+  };
+  if (plain.on()) {
+    policy("Plain", "PlainCfg", plain);
+    snprintf(buf, sizeof(buf), "extern \"C\" __global__ void __launch_bounds__(%d) CRBM_GIBBS_ATTR crbm_gibbs_sparse_geo(crbm::GibbsArgs a) { crbm::gibbs_geo_body<PlainCfg, PlainGeo>(a); }\n", plain.threads);
+    s += buf;
+  }
+  if (fused.on()) {
+    policy("Fused", "FusedCfg", fused);
+    snprintf(buf, sizeof(buf),
+             "extern \"C\" __global__ void __launch_bounds__(%d) CRBM_GIBBS_ATTR crbm_gibbs_sparse_stats_geo(crbm::GibbsArgs a) { if constexpr (FusedCfg::FUSE_STATS) crbm::gibbs_body<FusedCfg, true, true, FusedGeo>(a); }\n"
+             "extern \"C\" __global__ void __launch_bounds__(%d) CRBM_GIBBS_ATTR crbm_train_local_geo(crbm::TrainLocalArgs a) { crbm::train_local_body<FusedCfg, FusedGeo>(a); }\n",
+             fused.threads, fused.threads);
+    s += buf;
+  }
+  return s;
+}
+
+inline int jit_compile_source(const std::string& stub, std::vector<char>* code, bool* from_cache, std::string* cache_file, std::string* err);
+
 // Compile (or fetch from the cache) the code object; no device needed.
 inline int jit_compile(int K, int M, int DS, int G, int GS, int POOL, int gibbs_wpe, int gibbs_tb, std::vector<char>* code, bool* from_cache,
                        std::string* cache_file, std::string* err, bool slab = false) {
+  return jit_compile_source(jit_stub(K, M, DS, G, GS, POOL, gibbs_wpe, gibbs_tb, slab), code, from_cache, cache_file, err);
+}
+inline int jit_compile_geo(int K, int M, int DS, int POOL, int gibbs_wpe, const JitGeo& plain, const JitGeo& fused, std::vector<char>* code,
+                           bool* from_cache, std::string* cache_file, std::string* err) {
+  return jit_compile_source(jit_geo_stub(K, M, DS, POOL, gibbs_wpe, plain, fused), code, from_cache, cache_file, err);
+}
+
+inline int jit_compile_source(const std::string& stub, std::vector<char>* code, bool* from_cache, std::string* cache_file, std::string* err) {
   const std::string dir = jit_source_dir();
   std::string kernels, layout;
   if (!jit_read_file(dir + "/crbm_kernels.h", &kernels) || !jit_read_file(dir + "/crbm_layout.h", &layout)) {
     *err = "kernel sources not found in " + dir + " (set CRBM_KERNEL_SRC_DIR)";
     return -1;
   }
-  const std::string stub = jit_stub(K, M, DS, G, GS, POOL, gibbs_wpe, gibbs_tb, slab);
   std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                                    "-I" + dir, "-I/opt/rocm/include"};
   if (const char* e = getenv("CRBM_JIT_DEFINES")) {   // tuning knobs, e.g. "-DCRBM_STATS_MAX_TILES=16"
@@ -212,6 +263,35 @@ inline int jit_load(int K, int M, int DS, int G, int GS, int POOL, int gibbs_wpe
       {"crbm_mutagenesis", &out->mutagenesis}, {"crbm_ais", &out->ais}, {"crbm_scan_sites", &out->scan_sites},
       {"crbm_scan_hist", &out->scan_hist}, {"crbm_variant_effects", &out->variant_effects}};
   for (auto& s : syms) {
+    e = hipModuleGetFunction(s.f, out->module, s.name);
+    if (e != hipSuccess) {
+      *err = std::string("hipModuleGetFunction(") + s.name + "): " + hipGetErrorString(e);
+      return -1;
+    }
+  }
+  return 0;
+}
+
+// the geometry-specialised chain kernels of a handle; a function stays null where the plan has no such launch shape
+struct JitGeoKernels {
+  hipModule_t module = nullptr;
+  hipFunction_t gibbs_sparse = nullptr, gibbs_sparse_stats = nullptr, train_local = nullptr;
+};
+inline int jit_load_geo(int K, int M, int DS, int POOL, int gibbs_wpe, const JitGeo& plain, const JitGeo& fused, JitGeoKernels* out, std::string* err) {
+  if (!plain.on() && !fused.on()) return 0;
+  std::vector<char> code;
+  bool cached = false;
+  if (jit_compile_geo(K, M, DS, POOL, gibbs_wpe, plain, fused, &code, &cached, nullptr, err) != 0) return -1;
+  hipError_t e = hipModuleLoadData(&out->module, code.data());
+  if (e != hipSuccess) {
+    *err = std::string("hipModuleLoadData: ") + hipGetErrorString(e);
+    return -1;
+  }
+  struct { bool want; const char* name; hipFunction_t* f; } syms[] = {
+      {plain.on(), "crbm_gibbs_sparse_geo", &out->gibbs_sparse}, {fused.on(), "crbm_gibbs_sparse_stats_geo", &out->gibbs_sparse_stats},
+      {fused.on(), "crbm_train_local_geo", &out->train_local}};
+  for (auto& s : syms) {
+    if (!s.want) continue;
     e = hipModuleGetFunction(s.f, out->module, s.name);
     if (e != hipSuccess) {
       *err = std::string("hipModuleGetFunction(") + s.name + "): " + hipGetErrorString(e);

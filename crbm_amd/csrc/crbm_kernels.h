@@ -1334,6 +1334,50 @@ struct GibbsArgs {
   StatsGeom sg;        // divGPC divides group indices of one tile
 };
 
+// The geometry of a chain launch as gibbs_body sees it.  GeomRT reads it from the arguments (FastDiv records for the
+// index divisions), serves any launch and carries the profiling aids (debug, clock, timeline).  GeomCT has the geometry
+// of ONE launch shape compiled in (crbm_jit.h, jit_geo_stub; the host picks it only for a launch of exactly this shape:
+// crbm_plan.h, GeoSpec): divisions by constants, one state-load path, constant trip counts, a single tile per block
+// where the grid covers every tile, and nothing of the profiling aids.  Every tile of a GeomCT launch is full
+// (NCHAINS % S == 0).  Both forms compute the same bits: the geometry decides where a word lives, never its value.
+struct GeomRT {
+  static constexpr bool CT = false, PROF = true, ALIGNED = false, ONE = false;
+  const GibbsArgs& a;
+  __device__ __forceinline__ explicit GeomRT(const GibbsArgs& a_) : a(a_) {}
+  __device__ __forceinline__ int S() const { return a.S; }
+  __device__ __forceinline__ int Lf() const { return a.Lf; }
+  __device__ __forceinline__ int Lv() const { return a.Lv; }
+  __device__ __forceinline__ int Lrow() const { return a.Lrow; }
+  __device__ __forceinline__ int LWs() const { return a.LWs; }
+  __device__ __forceinline__ int nvb() const { return a.nvb; }
+  __device__ __forceinline__ int nhb() const { return a.nhb; }
+  __device__ __forceinline__ int nchains() const { return a.nchains; }
+  __device__ __forceinline__ uint32_t threads() const { return blockDim.x; }
+  __device__ __forceinline__ int nblk() const { return a.nblocks > 0 ? a.nblocks : (int)gridDim.x; }
+  __device__ __forceinline__ uint32_t div_vb(uint32_t i) const { return fastdiv_tile(i, a.divVB); }
+  __device__ __forceinline__ uint32_t div_hb(uint32_t i) const { return fastdiv_tile(i, a.divHB); }
+  template <int NW> __device__ __forceinline__ uint32_t div_lfw(uint32_t i) const { return fastdiv_tile(i, a.divLfw); }
+};
+template <int S_, int LF_, int LV_, int LROW_, int LWS_, int NVB_, int NHB_, int TB_, int NCHAINS_, int GRID_, bool ALIGNED_>
+struct GeomCT {
+  static_assert(S_ >= 1 && NCHAINS_ % S_ == 0 && GRID_ >= 1 && GRID_ <= NCHAINS_ / S_ && TB_ % 64 == 0, "GeomCT: full tiles only");
+  static constexpr bool CT = true, PROF = false, ALIGNED = ALIGNED_, ONE = GRID_ == NCHAINS_ / S_;
+  __device__ __forceinline__ explicit GeomCT(const GibbsArgs&) {}
+  __device__ __forceinline__ constexpr int S() const { return S_; }
+  __device__ __forceinline__ constexpr int Lf() const { return LF_; }
+  __device__ __forceinline__ constexpr int Lv() const { return LV_; }
+  __device__ __forceinline__ constexpr int Lrow() const { return LROW_; }
+  __device__ __forceinline__ constexpr int LWs() const { return LWS_; }
+  __device__ __forceinline__ constexpr int nvb() const { return NVB_; }
+  __device__ __forceinline__ constexpr int nhb() const { return NHB_; }
+  __device__ __forceinline__ constexpr int nchains() const { return NCHAINS_; }
+  __device__ __forceinline__ constexpr uint32_t threads() const { return TB_; }
+  __device__ __forceinline__ constexpr int nblk() const { return GRID_; }
+  __device__ __forceinline__ uint32_t div_vb(uint32_t i) const { return i / (uint32_t)NVB_; }
+  __device__ __forceinline__ uint32_t div_hb(uint32_t i) const { return i / (uint32_t)NHB_; }
+  template <int NW> __device__ __forceinline__ uint32_t div_lfw(uint32_t i) const { return i / (uint32_t)(LF_ * NW); }
+};
+
 // letter of one visible position from its 4 top-down activations, given in units of log 2 (the tables carry log2(e))
 __device__ __forceinline__ uint32_t sample_letter(float y0, float y1, float y2, float y3, float u) {
   const float mx = fmaxf(fmaxf(y0, y1), fmaxf(y2, y3));
@@ -1383,8 +1427,12 @@ __device__ __forceinline__ void topdown_bits(unsigned long long w, const char* t
 // in wave units of two 32-position groups, every lane parks the probabilities it has in
 // registers anyway in the wave's LDS slice, and the wave contracts them with the visible
 // sample (still in LDS) on the matrix cores -- no second read of v, no recomputation of P.
-template <class C, bool SPARSE, bool STATS = false>
+// GP: the geometry policy (GeomRT: any launch; GeomCT: one launch shape, compiled in).
+template <class C, bool SPARSE, bool STATS = false, class GP = GeomRT>
 __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block of the chain grid (default: blockIdx.x)
+  const GP g(a);
+  const int dbg = GP::PROF ? a.debug : 0;              // profiling only (GibbsArgs::debug)
+  const uint32_t TB = g.threads();
   constexpr int KP = C::KP, M = C::M, NW = C::NW, NCH = C::NCH;
   static_assert(SPARSE || C::DENSE, "no dense top-down tables for this model");
   using SR = StatsRole<C, false>;
@@ -1394,9 +1442,9 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
   const float* Tf = smem;
   const float* cv = smem + (SPARSE ? C::SP_C : C::OFF_C);
   uint32_t* hm = reinterpret_cast<uint32_t*>(smem + LTAB);
-  uint32_t* hmp = hm + (size_t)a.S * a.Lrow * NW;
-  uint32_t* let = hmp + (C::DS ? (size_t)a.S * a.Lrow * NW : 0);
-  uint32_t* fixq = let + (size_t)a.S * a.LWs;   // [count][-][FIXQ_CAP entries]: undecided units of the running h|v pass
+  uint32_t* hmp = hm + (size_t)g.S() * g.Lrow() * NW;
+  uint32_t* let = hmp + (C::DS ? (size_t)g.S() * g.Lrow() * NW : 0);
+  uint32_t* fixq = let + (size_t)g.S() * g.LWs();   // [count][-][FIXQ_CAP entries]: undecided units of the running h|v pass
 #ifdef CRBM_INLINE_EXACT_PATH                     // A/B knob (CRBM_JIT_DEFINES): every wave resolves its own undecided units
   constexpr bool DEFER = false;
 #else
@@ -1408,7 +1456,7 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
 #endif
 
   // The tables are copied while the state loads of the block's first tile are in flight (below).
-  bool tables_done = (a.debug & 1) != 0;
+  bool tables_done = (dbg & 1) != 0;
   auto copy_all_tables = [&]() {
     if (SPARSE) {
       copy_tables<C::TAB>(smem, a.tables_tf ? a.tables_tf : a.tables);
@@ -1419,19 +1467,21 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
     tables_done = true;
   };
 
-  const int rowW = a.Lrow * NW;
-  const uint32_t per = (uint32_t)(a.Lf * NW);           // state words per chain
-  const int ntiles = (a.nchains + a.S - 1) / a.S;
+  const int rowW = g.Lrow() * NW;
+  const uint32_t per = (uint32_t)(g.Lf() * NW);           // state words per chain
+  const int ntiles = (g.nchains() + g.S() - 1) / g.S();
   if (bid < 0) bid = (int)blockIdx.x;
-  if (a.clock && bid == 0 && threadIdx.x == 0) {        // both clocks at the start of the launch, parked in memory (no live registers)
-    a.clock[2] = realtime_ticks();
-    a.clock[3] = shader_cycles();
+  if constexpr (GP::PROF) {
+    if (a.clock && bid == 0 && threadIdx.x == 0) {      // both clocks at the start of the launch, parked in memory (no live registers)
+      a.clock[2] = realtime_ticks();
+      a.clock[3] = shader_cycles();
+    }
+    if (a.timeline && bid == 0 && threadIdx.x == 0) a.timeline[0] = realtime_ticks();
   }
-  if (a.timeline && bid == 0 && threadIdx.x == 0) a.timeline[0] = realtime_ticks();
-  const int nblk = a.nblocks > 0 ? a.nblocks : (int)gridDim.x;
+  const int nblk = g.nblk();
   int nset = 0;
   // statistics state (STATS): the wave's LDS slice, accumulator tiles, letter counts
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = TB >> 6;
   float* sreg = nullptr;
   uint32_t* swin = nullptr;
   float* sPt = nullptr;
@@ -1451,38 +1501,39 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
   // the pads of the mask rows (M-1 positions in front, the rest behind) stay zero for the whole kernel
   {
     const int padw = rowW - (int)per, front = (M - 1) * NW;
-    for (int idx = threadIdx.x; idx < a.S * padw; idx += blockDim.x) {
+    for (int idx = threadIdx.x; idx < g.S() * padw; idx += TB) {
       const int nl = idx / padw, e = idx - nl * padw;
       const int d = nl * rowW + (e < front ? e : e + (int)per);
       hm[d] = 0u;
       if (C::DS) hmp[d] = 0u;
     }
   }
-  for (int tile = bid; tile < ntiles; tile += nblk) {
-    const int n0 = tile * a.S;
-    const int ns = min(a.S, a.nchains - n0);
+  // (GeomCT: every tile is full; where the grid covers all tiles the loop is one iteration without a test)
+  for (int tile = bid; GP::ONE ? tile == bid : tile < ntiles; tile += nblk) {
+    const int n0 = tile * g.S();
+    const int ns = GP::CT ? g.S() : min(g.S(), g.nchains() - n0);
     __syncthreads();
     // chain state -> zero-padded LDS rows (hidden position s sits at s + M-1).  The
     // chains of a tile are one contiguous range of ns*per words in global memory:
     // all loads of a thread are issued before the first LDS store (one memory round
     // trip per tile), 16 bytes per lane where the alignment allows.
-    if (!(a.debug & 2)) {
+    if (!(dbg & 2)) {
       const uint32_t nwords = (uint32_t)ns * per;
       auto lds_index = [&](uint32_t i) {           // word i of the tile -> padded row position
-        const uint32_t nl = fastdiv_tile(i, a.divLfw);
+        const uint32_t nl = g.template div_lfw<NW>(i);
         return nl * (uint32_t)rowW + (uint32_t)((M - 1) * NW) + (i - nl * per);
       };
       const size_t g0 = (size_t)n0 * per;
-      if (((g0 | nwords) & 3u) == 0u) {
+      if (GP::CT ? GP::ALIGNED : ((g0 | nwords) & 3u) == 0u) {
         constexpr int UN = 2;
         const uint4* src = reinterpret_cast<const uint4*>(a.hm + g0);
         const uint4* srcp = C::DS ? reinterpret_cast<const uint4*>(a.hmp + g0) : nullptr;
-        for (uint32_t base0 = 0; base0 < nwords / 4; base0 += UN * blockDim.x) {   // the same rounds for every thread
+        for (uint32_t base0 = 0; base0 < nwords / 4; base0 += UN * TB) {   // the same rounds for every thread
           const uint32_t base = base0 + threadIdx.x;
           uint4 t[UN], tp[UN];
 #pragma unroll
           for (int u = 0; u < UN; ++u) {
-            const uint32_t i4 = base + u * blockDim.x;
+            const uint32_t i4 = base + u * TB;
             if (i4 < nwords / 4) {
               t[u] = src[i4];
               if (C::DS) tp[u] = srcp[i4];
@@ -1491,7 +1542,7 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
           if (!tables_done) copy_all_tables();
 #pragma unroll
           for (int u = 0; u < UN; ++u) {
-            const uint32_t i4 = base + u * blockDim.x;
+            const uint32_t i4 = base + u * TB;
             if (i4 < nwords / 4) {
               const uint32_t e[4] = {t[u].x, t[u].y, t[u].z, t[u].w};
               const uint32_t ep[4] = {tp[u].x, tp[u].y, tp[u].z, tp[u].w};
@@ -1506,12 +1557,12 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
         }
       } else {
         constexpr int UN = 8;
-        for (uint32_t base0 = 0; base0 < nwords; base0 += UN * blockDim.x) {
+        for (uint32_t base0 = 0; base0 < nwords; base0 += UN * TB) {
           const uint32_t base = base0 + threadIdx.x;
           uint32_t t[UN], tp[UN];
 #pragma unroll
           for (int u = 0; u < UN; ++u) {
-            const uint32_t i = base + u * blockDim.x;
+            const uint32_t i = base + u * TB;
             if (i < nwords) {
               t[u] = a.hm[g0 + i];
               if (C::DS) tp[u] = a.hmp[g0 + i];
@@ -1520,7 +1571,7 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
           if (!tables_done) copy_all_tables();
 #pragma unroll
           for (int u = 0; u < UN; ++u) {
-            const uint32_t i = base + u * blockDim.x;
+            const uint32_t i = base + u * TB;
             if (i < nwords) {
               const uint32_t d = lds_index(i);
               hm[d] = t[u];
@@ -1531,7 +1582,7 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
       }
     }
     if (!tables_done) copy_all_tables();
-    for (int idx = threadIdx.x; idx < ns * a.LWs; idx += blockDim.x) let[idx] = 0u;
+    for (int idx = threadIdx.x; idx < ns * g.LWs(); idx += TB) let[idx] = 0u;
     // The exact path of the hidden sampler, block-wide (DEFER).  A unit whose coarse 12-bit field cannot
     // decide it (2^-12 of all units, but some lane of a wave in 14.5 % of all rounds at K = 10) is not
     // resolved by its wave -- that costs the whole wave a second Philox call and a pass over its ten
@@ -1540,10 +1591,10 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
     // both Philox calls, the exact comparison of sample_hidden, one atomic OR into the mask word.
     auto resolve = [&](uint32_t e, int st, bool last) -> uint32_t {
       const uint32_t it = e & 0xFFFFFu, k = (e >> 20) & 0x7FFu, strand = e >> 31;
-      const uint32_t nl = fastdiv_tile(it, a.divHB);
-      const int s = (int)(it - nl * (uint32_t)a.nhb);
+      const uint32_t nl = g.div_hb(it);
+      const int s = (int)(it - nl * (uint32_t)g.nhb());
       const uint32_t gn = a.rng.seq_offset + (uint32_t)(n0 + nl);
-      LetterWin<M> win = letter_window<M>(let + nl * (uint32_t)a.LWs, s);
+      LetterWin<M> win = letter_window<M>(let + nl * (uint32_t)g.LWs(), s);
       if (strand) win = revcomp_window<M>(win);
       const float* T = Tf + k;
       float z = 0.f;
@@ -1561,7 +1612,7 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
       const uint32_t one = frac * 4096.0f > (float)philox_field12_dyn(rf, (int)i10) ? 1u : 0u;
       if (one) {
         const uint32_t bit = 1u << (k & 31u), w = k >> 5;
-        if (last) { if (!(a.debug & 4)) atomicOr((strand ? a.hmp : a.hm) + (size_t)n0 * per + it * (uint32_t)NW + w, bit); }
+        if (last) { if (!(dbg & 4)) atomicOr((strand ? a.hmp : a.hm) + (size_t)n0 * per + it * (uint32_t)NW + w, bit); }
         else atomicOr((strand ? hmp : hm) + (nl * (uint32_t)(rowW - (int)per) + it * (uint32_t)NW + (uint32_t)((M - 1) * NW)) + w, bit);
       }
       return one;
@@ -1593,7 +1644,7 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
       if (last) wait_vector_memory();
       __syncthreads();                                // every mask word of the pass is stored, every entry queued
       const uint32_t nq = min(fixq[0], (uint32_t)FIXQ_CAP);
-      for (uint32_t e = threadIdx.x; e < nq; e += blockDim.x) {
+      for (uint32_t e = threadIdx.x; e < nq; e += TB) {
         const uint32_t one = resolve(fixq[2 + e], st, last);
         if (last) nset += (int)one;
       }
@@ -1602,9 +1653,9 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
       __syncthreads();
       if (threadIdx.x == 0) fixq[0] = 0u;             // read by drain_queue before this barrier, filled again after the next
       // ---- v | h : y[a,p] = c[a] + sum_{k,j} W[k,a,j] h[k,p-j] (+ rc strand) ----
-      for (uint32_t it = threadIdx.x; it < (uint32_t)(ns * a.nvb); it += blockDim.x) {
-        const uint32_t nl = fastdiv_tile(it, a.divVB);
-        const int pb = (int)(it - nl * (uint32_t)a.nvb);
+      for (uint32_t it = threadIdx.x; it < (uint32_t)(ns * g.nvb()); it += TB) {
+        const uint32_t nl = g.div_vb(it);
+        const int pb = (int)(it - nl * (uint32_t)g.nvb());
         const int p0 = 4 * pb;
         float y[4][4];
 #pragma unroll
@@ -1615,7 +1666,7 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
           constexpr int NMV = (M + 3 + 3) / 4;
 #pragma unroll
           for (int strand = 0; strand <= C::DS; ++strand) {
-            const uint4* mrow = reinterpret_cast<const uint4*>((strand ? hmp : hm) + (size_t)nl * a.Lrow + p0);
+            const uint4* mrow = reinterpret_cast<const uint4*>((strand ? hmp : hm) + (size_t)nl * g.Lrow() + p0);
             const char* Tv = reinterpret_cast<const char*>(smem + (strand ? C::OFF_TVR : C::OFF_TV));
             uint32_t off[4 * NMV][NCH];
 #pragma unroll
@@ -1647,7 +1698,7 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
           constexpr int NWORD = (NSLOT + PPW - 1) / PPW;
 #pragma unroll
           for (int strand = 0; strand <= C::DS; ++strand) {
-            const uint32_t* mrow = (strand ? hmp : hm) + ((size_t)nl * a.Lrow + p0) * NW;
+            const uint32_t* mrow = (strand ? hmp : hm) + ((size_t)nl * g.Lrow() + p0) * NW;
             const char* tab = reinterpret_cast<const char*>(smem + (strand ? C::SP_WSR : C::SP_WS));
             if constexpr (NW == 1) {
               constexpr int NMV = (NSLOT + 3) / 4;
@@ -1691,9 +1742,9 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const uint32_t l = sample_letter(y[i][0], y[i][1], y[i][2], y[i][3], u01(r.v[i]));
-          byte |= (p0 + i < a.Lv ? l : 0u) << (2 * i);
+          byte |= (p0 + i < g.Lv() ? l : 0u) << (2 * i);
         }
-        reinterpret_cast<unsigned char*>(let + (size_t)nl * a.LWs)[pb] = (unsigned char)byte;
+        reinterpret_cast<unsigned char*>(let + (size_t)nl * g.LWs())[pb] = (unsigned char)byte;
       }
       __syncthreads();
       bool fused_pass = false;
@@ -1712,9 +1763,9 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
             if (G < ngl) {
               const uint32_t nl = fastdiv_tile((uint32_t)G, a.sg.divGPC);
               gi = G - (int)nl * GPC;
-              if (2 * gi + w < a.LWs) word = let[(size_t)nl * a.LWs + 2 * gi + w];
+              if (2 * gi + w < g.LWs()) word = let[(size_t)nl * g.LWs() + 2 * gi + w];
             }
-            vcount += stats_window_piece<NPW>(reinterpret_cast<unsigned short*>(swin), lane, word, G < ngl, gi, GPC, a.Lv);
+            vcount += stats_window_piece<NPW>(reinterpret_cast<unsigned short*>(swin), lane, word, G < ngl, gi, GPC, g.Lv());
           }
           __builtin_amdgcn_wave_barrier();
           {
@@ -1725,12 +1776,12 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
             if (valid) {
               nl = fastdiv_tile((uint32_t)G, a.sg.divGPC);
               s = 32 * (G - (int)nl * GPC) + (lane & 31);
-              valid = s < a.Lf;
+              valid = s < g.Lf();
             }
             float* col = sPt + lane;
             if (valid) {
               const uint32_t gn = a.rng.seq_offset + (uint32_t)(n0 + nl);
-              const LetterWin<M> win = letter_window<M>(let + (size_t)nl * a.LWs, s);
+              const LetterWin<M> win = letter_window<M>(let + (size_t)nl * g.LWs(), s);
 #pragma unroll
               for (int strand = 0; strand <= C::DS; ++strand) {
                 float x[KP], p[KP];
@@ -1743,10 +1794,10 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
                 uint32_t* dst = (strand ? a.hmp : a.hm) + (size_t)(n0 + nl) * per + (size_t)s * NW;
 #pragma unroll
                 for (int w = 0; w < NW; ++w) {
-                  if (!(a.debug & 4)) store1_streaming(dst + w, mask[w]);
+                  if (!(dbg & 4)) store1_streaming(dst + w, mask[w]);
                   nset += __popc(mask[w]);
                 }
-                if constexpr (DEFER) nset += (int)defer_units(pend, nl * (uint32_t)a.nhb + (uint32_t)s, (uint32_t)strand, st, true);
+                if constexpr (DEFER) nset += (int)defer_units(pend, nl * (uint32_t)g.nhb() + (uint32_t)s, (uint32_t)strand, st, true);
 #pragma unroll
                 for (int k = 0; k < C::K; ++k) col[(size_t)(strand * KW + k) * STATS_RS] = p[k];
               }
@@ -1768,11 +1819,11 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
       // one hidden position per item (nhb = Lf items per chain): the K units of a position
       // already give the instruction-level parallelism, and single positions spread evenly
       // over the waves of the block
-      for (uint32_t it = threadIdx.x; it < (uint32_t)(ns * a.nhb); it += blockDim.x) {
-        const uint32_t nl = fastdiv_tile(it, a.divHB);
-        const int s = (int)(it - nl * (uint32_t)a.nhb);
+      for (uint32_t it = threadIdx.x; it < (uint32_t)(ns * g.nhb()); it += TB) {
+        const uint32_t nl = g.div_hb(it);
+        const int s = (int)(it - nl * (uint32_t)g.nhb());
         const uint32_t gn = a.rng.seq_offset + (uint32_t)(n0 + nl);
-        const uint32_t* lrow = let + nl * (uint32_t)a.LWs;        // LDS offsets: 32-bit arithmetic
+        const uint32_t* lrow = let + nl * (uint32_t)g.LWs();        // LDS offsets: 32-bit arithmetic
         const LetterWin<M> win = letter_window<M>(lrow, s);
 #pragma unroll
         for (int strand = 0; strand <= C::DS; ++strand) {
@@ -1799,7 +1850,7 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
             uint32_t* dst = (strand ? a.hmp : a.hm) + (size_t)n0 * per + it * (uint32_t)NW;
 #pragma unroll
             for (int w = 0; w < NW; ++w) {
-              if (!(a.debug & 4)) store1_streaming(dst + w, mask[w]);
+              if (!(dbg & 4)) store1_streaming(dst + w, mask[w]);
               nset += __popc(mask[w]);
             }
           } else {
@@ -1818,42 +1869,62 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
     }
     // LDS -> chain state (contiguous in global memory, 16-byte stores where aligned): only a launch
     // without steps (state round trip) still has the state in LDS here
-    if (a.steps == 0) __syncthreads();
-    if (a.steps == 0 && !(a.debug & 4)) {
+    // (GeomCT launches always step: the host sends a launch without steps to the run-time form)
+    const bool round_trip = !GP::CT && a.steps == 0;
+    if (round_trip) __syncthreads();
+    if (round_trip && !(dbg & 4)) {
       const uint32_t nwords = (uint32_t)ns * per;
       const size_t g0 = (size_t)n0 * per;
       auto lds_index = [&](uint32_t i) {
-        const uint32_t nl = fastdiv_tile(i, a.divLfw);
+        const uint32_t nl = g.template div_lfw<NW>(i);
         return nl * (uint32_t)rowW + (uint32_t)((M - 1) * NW) + (i - nl * per);
       };
       if (((g0 | nwords) & 3u) == 0u) {
-        for (uint32_t i4 = threadIdx.x; i4 < nwords / 4; i4 += blockDim.x) {
+        for (uint32_t i4 = threadIdx.x; i4 < nwords / 4; i4 += TB) {
           const uint32_t d0 = lds_index(4 * i4), d1 = lds_index(4 * i4 + 1), d2 = lds_index(4 * i4 + 2), d3 = lds_index(4 * i4 + 3);
           store4_streaming(a.hm + g0 + 4 * (size_t)i4, hm[d0], hm[d1], hm[d2], hm[d3]);
           if (C::DS) store4_streaming(a.hmp + g0 + 4 * (size_t)i4, hmp[d0], hmp[d1], hmp[d2], hmp[d3]);
         }
       } else {
-        for (uint32_t i = threadIdx.x; i < nwords; i += blockDim.x) {
+        for (uint32_t i = threadIdx.x; i < nwords; i += TB) {
           const uint32_t d = lds_index(i);
           a.hm[g0 + i] = hm[d];
           if (C::DS) a.hmp[g0 + i] = hmp[d];
         }
       }
     }
-    if (a.vout && !(a.debug & 4))
-      for (int idx = threadIdx.x; idx < ns * a.LWs; idx += blockDim.x)
-        a.vout[(size_t)n0 * a.LWs + idx] = let[idx];
+    if (a.vout && !(dbg & 4))
+      for (int idx = threadIdx.x; idx < ns * g.LWs(); idx += TB)
+        a.vout[(size_t)n0 * g.LWs() + idx] = let[idx];
   }
   if (a.ones) {   // one plain store per wave, summed by the host (counts stay far below 2^24: exact in float)
     const float tot = wave_sum((float)nset);
-    if ((threadIdx.x & 63) == 0) a.ones[bid * (blockDim.x >> 6) + (threadIdx.x >> 6)] = (uint32_t)tot;
+    if ((threadIdx.x & 63) == 0) a.ones[bid * (TB >> 6) + (threadIdx.x >> 6)] = (uint32_t)tot;
   }
-  if (a.clock && bid == 0 && threadIdx.x == 0) {
+  if constexpr (GP::PROF) {
+    if (a.clock && bid == 0 && threadIdx.x == 0) {
+      a.clock[0] += realtime_ticks() - a.clock[2];
+      a.clock[1] += shader_cycles() - a.clock[3];
+    }
+    if (a.timeline && bid == 0 && threadIdx.x == 0) a.timeline[1] = realtime_ticks();
+  }
+  if constexpr (STATS) stats_mfma_finish<C, false>(a.sg, smem, 0, bid, sacc, vcount);
+}
+
+// A plain chain launch in a compiled-in geometry.  The timed launches still sample both clocks (GibbsArgs::clock,
+// crbm_last_shader_clock), here around the body: one scalar test per wave, the reads on block 0's first thread alone.
+template <class C, class GP>
+__device__ void gibbs_geo_body(const GibbsArgs& a) {
+  const bool timed = a.clock && blockIdx.x == 0 && threadIdx.x == 0;
+  if (timed) {
+    a.clock[2] = realtime_ticks();
+    a.clock[3] = shader_cycles();
+  }
+  gibbs_body<C, true, false, GP>(a);
+  if (timed) {
     a.clock[0] += realtime_ticks() - a.clock[2];
     a.clock[1] += shader_cycles() - a.clock[3];
   }
-  if (a.timeline && bid == 0 && threadIdx.x == 0) a.timeline[1] = realtime_ticks();
-  if constexpr (STATS) stats_mfma_finish<C, false>(a.sg, smem, 0, bid, sacc, vcount);
 }
 
 // The local phase of a training step in ONE launch (convRBM.py:373-413): g.nblocks blocks advance the
@@ -1867,13 +1938,13 @@ struct TrainLocalArgs {
   StatsMfmaArgs d;
 };
 
-template <class C>
+template <class C, class GP = GeomRT>
 __device__ void train_local_body(const TrainLocalArgs& a) {
   if constexpr (C::FUSE_STATS) {
     const int nG = a.g.nblocks, nD = a.d.nblocks, m = min(nG, nD), b = (int)blockIdx.x;
     const bool chain = b < 2 * m ? !(b & 1) : nG > nD;      // alternate while both kinds last, then the rest
     const int idx = b < 2 * m ? b >> 1 : b - m;
-    if (chain) gibbs_body<C, true, true>(a.g, idx);
+    if (chain) gibbs_body<C, true, true, GP>(a.g, idx);
     else stats_mfma_body<C, true, false>(a.d, idx);
   }
 }

@@ -189,6 +189,28 @@ inline int slab_choose(int K, int M, int ds, int pool, int Lf, int* G_out, Model
 // the geometry of one kind of chain launch; off (threads == 0) where the model has no launch of that kind
 struct ChainGeom { GibbsLayout gl = {}; int threads = 0, grid = 0; bool on() const { return threads > 0; } };
 
+// A chain launch shape whose kernels are compiled for exactly this geometry (crbm_kernels.h, GeomCT; crbm_jit.h,
+// jit_geo_stub): the layout, the block, the grid and the number of chains of ONE launch, all tiles full.  A launch of any
+// other shape (a ragged last partition, a launch without steps, profiling aids) takes the run-time form of the model's
+// own module.  group: letters per gather-table group of the kernel's Cfg.
+struct GeoSpec {
+  GibbsLayout gl = {};
+  int threads = 0, grid = 0, nchains = 0, group = 0;
+  bool aligned = false;         // every tile's state starts and ends on a 16-byte boundary
+  bool on() const { return threads > 0; }
+  bool serves(const GibbsLayout& l, int threads_, int grid_, int nchains_) const {
+    return on() && l.S == gl.S && l.Lv == gl.Lv && l.nvb == gl.nvb && l.nhb == gl.nhb && l.Lrow == gl.Lrow && l.LWs == gl.LWs &&
+           threads_ == threads && grid_ == grid && nchains_ == nchains;
+  }
+};
+inline GeoSpec geo_spec(const GibbsLayout& gl, int threads, int grid, int nchains, int NW, int group) {
+  GeoSpec s;
+  if (threads <= 0 || threads % 64 || gl.S < 1 || nchains < gl.S || nchains % gl.S || grid < 1 || grid > nchains / gl.S) return s;
+  s.gl = gl; s.threads = threads; s.grid = grid; s.nchains = nchains; s.group = group;
+  s.aligned = ((long)gl.S * gl.nhb * NW) % 4 == 0;
+  return s;
+}
+
 struct LaunchPlan {
   bool big = false;             // model beyond the LDS-resident kernels: the generic "big" kernels serve every entry point
   int G = 0, GS = 0;            // letters per gather-table group: of the model, of plain chain launches (solo_group)
@@ -200,7 +222,9 @@ struct LaunchPlan {
   // Plain chain launches of short kernels go out as `chain_parts` launches of `part_chains` chains each, one stream per
   // partition: chains are independent, so partition p's step t+1 only waits for partition p's step t, and the drain of
   // one partition's kernel, the dispatch and the ramp of its next one are filled by the other partition's blocks on the
-  // same CUs (config #2: 20.9 -> 17.6 us per step of the whole batch).  `part` is the geometry of ONE partition's launch
+  // same CUs (config #2: 20.9 -> 17.6 us per step of the whole batch).  (What a one-step launch still costs beyond its
+  // step after that is not idle time: the counters show the vector issue busy for 0.92 of a step, i.e. instructions of
+  // the launch's fixed path -- which geo_plain / geo_fused below remove, not overlap.)  `part` is the geometry of ONE partition's launch
   // (chain_parts > 1); solo / chain[1] stay the unpartitioned one, which the chain launch INSIDE a training step takes
   // (one launch, then the statistics wait for it).
   ChainGeom part;
@@ -208,6 +232,16 @@ struct LaunchPlan {
   // what jit_compile / jit_load are keyed by: the register-allocation hint compiled into the sparse Gibbs kernel and
   // the block-size bound of the chain kernels (of the largest block any geometry above launches)
   int gibbs_wpe = 0, gibbs_tb = 256;
+  // Launch shapes with geometry-specialised chain kernels, a second code object keyed by them: of the plain launches
+  // of the API (one partition's where they go out in partitions) and of the chain half of the fused training launch
+  // (chain[1] with statistics).  CRBM_GEOM: 0 none (every launch in the run-time form), 1 (default) handles whose
+  // launch puts a tile on every CU -- below that a launch is over before its fixed path matters, and a handle of a few
+  // chains should not pay a second compile --, 2 every handle.
+  // Two shapes, not one per ChainGeom: where the plain launches go out in partitions (chain_parts > 1), an UNPARTITIONED
+  // plain launch of that handle (solo / chain[1]: crbm_gibbs_steps on another stream, the chain launch inside a
+  // training step of a model without fused statistics) is never specialised and takes the run-time form -- a third
+  // instantiation of the body would lengthen every crbm_create of such a handle for launches the hot paths do not make.
+  GeoSpec geo_plain, geo_fused;
   // the slab model of a generic DNA model (slab_choose); slab_K == 0: no slabs, slab_note says why
   int slab_K = 0, slab_G = 0;
   ModelShape slab_ms = {};
@@ -276,6 +310,16 @@ inline LaunchPlan plan_launches(int K, int M, int ds, int A, int pool, int Lf, i
   int threads = 0;
   for (const ChainGeom* g : {&p.chain[0], &p.chain[1], &p.solo, &p.part}) threads = std::max(threads, g->threads);
   p.gibbs_tb = gibbs_block_bound(threads);
+  const int geo_mode = env_int("CRBM_GEOM", 1);
+  if (geo_mode > 0 && !p.refusal) {
+    auto spec = [&](const ChainGeom& g, int nchains, int group) {
+      GeoSpec s = g.on() ? geo_spec(g.gl, g.threads, g.grid, nchains, p.ms.NW, group) : GeoSpec();
+      if (geo_mode == 1 && s.on() && nchains / s.gl.S < num_cu) s = GeoSpec();
+      return s;
+    };
+    p.geo_plain = p.chain_parts > 1 ? spec(p.part, p.part_chains, p.G) : spec(plain_geom(p, 1, false), B, p.GS);
+    if (p.ms.FUSE_STATS) p.geo_fused = spec(p.chain[1], B, p.G);
+  }
   return p;
 }
 

@@ -403,6 +403,9 @@ int crbm_copy_bandwidth(crbm_handle* h, int64_t bytes, int32_t reps, float* gb_p
  * block adds its duration in wall-clock ticks and in shader cycles): bench.py prices a step of overlapping launches in
  * shader cycles with it.  0 when unknown. */
 int crbm_last_shader_clock(crbm_handle* h, float* mhz);
+/* Chain kernel launches of this handle so far by the form of their geometry: compiled in (the kernels specialised on the
+ * handle's launch shapes; CRBM_GEOM) and read from the arguments (every other launch).  Either may be null. */
+int crbm_geometry_launches(const crbm_handle* h, int64_t* compiled_in, int64_t* run_time);
 /* Actual bytes of chain state one Gibbs launch reads+writes in HBM. */
 int64_t crbm_gibbs_state_bytes(const crbm_handle* h);
 
