@@ -61,6 +61,32 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 // a ^ b ^ c in one instruction (v_bitop3_b32, truth table 0x96); the compiler does not fuse it itself
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
 __device__ __forceinline__ uint32_t bitrev32(uint32_t x) { return __builtin_bitreverse32(x); }   // v_bfrev_b32
+// (x << SH) | acc in one instruction (v_lshl_or_b32): left to itself the compiler shifts two operands apart and joins
+// them with a v_or3_b32, three instructions where two of these do
+template <int SH>
+__device__ __forceinline__ uint32_t shl_or(uint32_t x, uint32_t acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t r;
+  asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "n"(SH), "v"(acc));
+  return r;
+#else
+  return (x << SH) | acc;
+#endif
+}
+// max of four finite floats in two instructions (v_max3_f32, v_max_f32).  fmaxf puts a canonicalising v_max_f32 x, x
+// in front of every operand the compiler cannot prove canonical (a value that may come straight from memory); no
+// operand here is ever a NaN, and the result is the same number whatever the order (with zeros of both signs among
+// the largest the sign of the result may differ: callers subtract it and take 2^x, which is 1 for either zero).
+__device__ __forceinline__ float max4_finite(float a, float b, float c, float d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  float m, r;
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(a), "v"(b), "v"(c));
+  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(m), "v"(d));
+  return r;
+#else
+  return fmaxf(fmaxf(a, b), fmaxf(c, d));
+#endif
+}
 // 16-byte store that does not linger in the caches (the chain state is written once
 // per launch and next read by another launch: measured 0.45 us per launch at config #2)
 __device__ __forceinline__ void store4_streaming(uint32_t* dst, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
@@ -123,6 +149,8 @@ typedef float floatx2 __attribute__((vector_size(8)));
 __device__ __forceinline__ floatx2 fma2(floatx2 a, floatx2 b, floatx2 c) { return floatx2{fmaf(a[0], b[0], c[0]), fmaf(a[1], b[1], c[1])}; }
 __device__ __forceinline__ floatx2 opaque(floatx2 v) { return v; }
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return a ^ b ^ c; }
+__device__ __forceinline__ float max4_finite(float a, float b, float c, float d) { return fmaxf(fmaxf(a, b), fmaxf(c, d)); }
+template <int SH> __device__ __forceinline__ uint32_t shl_or(uint32_t x, uint32_t acc) { return (x << SH) | acc; }
 __device__ __forceinline__ uint32_t bitrev32(uint32_t x) {
   x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
   x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
@@ -592,13 +620,43 @@ __device__ __forceinline__ void pooled_sample(const float (&p)[C::KP], const flo
   }
 }
 
-// global precomputed tables -> LDS (plain float4 copy; batching the loads of a thread measured slower)
+// global precomputed tables -> LDS (plain float4 copy, one load in flight per thread: with a run-time stride and trip
+// count, batching the loads of a thread measured slower).  stride: the threads of the block.
 template <int NFLOATS>
-__device__ __forceinline__ void copy_tables(float* dst, const float* src) {
+__device__ __forceinline__ void copy_tables(float* dst, const float* src, uint32_t stride) {
   static_assert(NFLOATS % 4 == 0, "tables are float4 granular");
   const float4* s4 = reinterpret_cast<const float4*>(src);
   float4* d4 = reinterpret_cast<float4*>(dst);
-  for (int i = threadIdx.x; i < NFLOATS / 4; i += blockDim.x) d4[i] = s4[i];
+  for (uint32_t i = threadIdx.x; i < (uint32_t)(NFLOATS / 4); i += stride) d4[i] = s4[i];
+}
+template <int NFLOATS>
+__device__ __forceinline__ void copy_tables(float* dst, const float* src) { copy_tables<NFLOATS>(dst, src, blockDim.x); }
+// Two tables, for a block of TB threads known at compile time (GeomCT): a thread's loads are all issued before its
+// first LDS store -- together with whatever loads the caller has in flight, one memory round trip instead of one per
+// 16 bytes -- in batches of at most CAP loads (4 * CAP registers; config #2: 4 + 1 loads, one batch).
+template <int NA, int NB, int TB>
+__device__ __forceinline__ void copy_tables_batched(float* dstA, const float* srcA, float* dstB, const float* srcB) {
+  static_assert(NA % 4 == 0 && NB % 4 == 0, "tables are float4 granular");
+  constexpr int A4 = NA / 4, B4 = NB / 4, RA = (A4 + TB - 1) / TB, RB = (B4 + TB - 1) / TB, R = RA + RB, CAP = 8;
+  const float4 *sA = reinterpret_cast<const float4*>(srcA), *sB = reinterpret_cast<const float4*>(srcB);
+  float4 *dA = reinterpret_cast<float4*>(dstA), *dB = reinterpret_cast<float4*>(dstB);
+  // round j of the two tables back to back: rounds [0, RA) are the first table's.  In a ragged last round the threads
+  // past the end copy the table's last element once more (the same 16 bytes to the same place): no branch around a
+  // load or a store, so nothing keeps the compiler from issuing every load first.
+#pragma unroll
+  for (int j0 = 0; j0 < R; j0 += CAP) {
+    float4 v[CAP];
+    int at[CAP];
+#pragma unroll
+    for (int c = 0; c < CAP; ++c) {
+      const int j = j0 + c, r = j < RA ? j : j - RA, n4 = j < RA ? A4 : B4, i = r * TB + (int)threadIdx.x;
+      at[c] = (r + 1) * TB <= n4 ? i : min(i, n4 - 1);
+      if (j < R) v[c] = (j < RA ? sA : sB)[at[c]];
+    }
+#pragma unroll
+    for (int c = 0; c < CAP; ++c)
+      if (j0 + c < R) (j0 + c < RA ? dA : dB)[at[c]] = v[c];
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1341,7 +1399,8 @@ struct GibbsArgs {
 // where the grid covers every tile, and nothing of the profiling aids.  Every tile of a GeomCT launch is full
 // (NCHAINS % S == 0).  Both forms compute the same bits: the geometry decides where a word lives, never its value.
 struct GeomRT {
-  static constexpr bool CT = false, PROF = true, ALIGNED = false, ONE = false;
+  static constexpr bool CT = false, PROF = true, ALIGNED = false, ONE = false, WHOLE_BYTES = false;
+  static constexpr int TB = 0;                          // the block size is the launch's
   const GibbsArgs& a;
   __device__ __forceinline__ explicit GeomRT(const GibbsArgs& a_) : a(a_) {}
   __device__ __forceinline__ int S() const { return a.S; }
@@ -1362,6 +1421,8 @@ template <int S_, int LF_, int LV_, int LROW_, int LWS_, int NVB_, int NHB_, int
 struct GeomCT {
   static_assert(S_ >= 1 && NCHAINS_ % S_ == 0 && GRID_ >= 1 && GRID_ <= NCHAINS_ / S_ && TB_ % 64 == 0, "GeomCT: full tiles only");
   static constexpr bool CT = true, PROF = false, ALIGNED = ALIGNED_, ONE = GRID_ == NCHAINS_ / S_;
+  static constexpr bool WHOLE_BYTES = LV_ % 4 == 0;     // every letter byte of a visible row holds four positions
+  static constexpr int TB = TB_;
   __device__ __forceinline__ explicit GeomCT(const GibbsArgs&) {}
   __device__ __forceinline__ constexpr int S() const { return S_; }
   __device__ __forceinline__ constexpr int Lf() const { return LF_; }
@@ -1379,12 +1440,50 @@ struct GeomCT {
 };
 
 // letter of one visible position from its 4 top-down activations, given in units of log 2 (the tables carry log2(e))
-__device__ __forceinline__ uint32_t sample_letter(float y0, float y1, float y2, float y3, float u) {
-  const float mx = fmaxf(fmaxf(y0, y1), fmaxf(y2, y3));
+// The letter is (t >= a) + (t >= b) + (t >= c) with t = u * sum(e) and the thresholds a = e0, b = e0 + e1, c = b + e2.
+// The thresholds ascend (every e >= 0, rounding is monotone), and t - x has exactly the sign of the comparison (a
+// difference of two floats never rounds to zero; t == x gives +0, which counts as t >= x).  With sa, sb, sc the sign
+// bits of t - a, t - b, t - c (sa => sb => sc), bit 1 of the letter is ~sb and bit 0 is ~(sa ^ sb ^ sc): one subtraction
+// per threshold and one v_bitop3 where compares, selects and adds took eight instructions and their wait states.
+// push_letter shifts the two bits INVERTED into acc (bit 1 first: v_alignbit, shift_in_sign), so that after the letters
+// of positions 3, 2, 1, 0 the low byte of ~acc is the packed letter byte of the four positions.
+// (The activations are finite sums of finite table entries: no NaN reaches a sign.)
+__device__ __forceinline__ uint32_t push_letter(uint32_t acc, float y0, float y1, float y2, float y3, float u) {
+  const float mx = max4_finite(y0, y1, y2, y3);
   const float e0 = __builtin_amdgcn_exp2f(y0 - mx), e1 = __builtin_amdgcn_exp2f(y1 - mx), e2 = __builtin_amdgcn_exp2f(y2 - mx),
               e3 = __builtin_amdgcn_exp2f(y3 - mx);
   const float t = u * ((e0 + e1) + (e2 + e3));
-  return (uint32_t)(t >= e0) + (uint32_t)(t >= e0 + e1) + (uint32_t)(t >= (e0 + e1) + e2);
+  const float da = t - e0, db = t - (e0 + e1), dc = t - ((e0 + e1) + e2);
+  acc = shift_in_sign(acc, db);
+  return (acc << 1) | (xor3(__float_as_uint(da), __float_as_uint(db), __float_as_uint(dc)) >> 31);
+}
+__device__ __forceinline__ uint32_t sample_letter(float y0, float y1, float y2, float y3, float u) {
+  return ~push_letter(0u, y0, y1, y2, y3, u) & 3u;
+}
+// the letter byte of the four positions p0 .. p0+3 of a visible row of Lv positions (p0 < Lv; letters beyond the row are 0):
+// `inv` holds their inverted bits as push_letter left them, position 3 pushed first.  FULL: Lv % 4 == 0, every byte is whole.
+template <bool FULL>
+__device__ __forceinline__ uint32_t letter_byte(uint32_t inv, int p0, int Lv) {
+  if constexpr (FULL) return ~inv & 0xFFu;
+  else return ~inv & (0xFFu >> (2 * max(0, 4 - (Lv - p0))));
+}
+
+// The first n of the masks m[T .. N) of K bits each join the two halves of a 64-bit window word, mask t at bit t*K,
+// in 32-bit shift-ors (lo and hi start at 0).  A mask that straddles bit 32 gives its low part to one half and the
+// rest to the other; it is the first piece of the upper half, as the mask at bit 32 is where none straddles.
+template <int K, int T, int N>
+__device__ __forceinline__ void pack_masks(const uint32_t* m, int n, uint32_t& lo, uint32_t& hi) {
+  if constexpr (T < N) {
+    constexpr int o = T * K;
+    if (T < n) {
+      if constexpr (o == 0) lo = m[T];
+      else if constexpr (o < 32) lo = shl_or<o % 32>(m[T], lo);
+      if constexpr (o < 32 && o + K > 32) hi = m[T] >> ((32 - o) % 32);
+      else if constexpr (o == 32) hi = m[T];
+      else if constexpr (o > 32) hi = shl_or<(o - 32) % 32>(m[T], hi);
+    }
+    pack_masks<K, T + 1, N>(m, n, lo, hi);
+  }
 }
 
 // Adds the top-down contributions of every set bit of one window word to the 4
@@ -1455,14 +1554,25 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
   constexpr bool DEFER = C::POOL == 1 && C::DS;
 #endif
 
-  // The tables are copied while the state loads of the block's first tile are in flight (below).
+  // The tables are copied while the state loads of the block's first tile are in flight (below).  GeomCT with one tile per
+  // block: the table loads join them -- every global load of the prologue is issued before the thread's first wait and
+  // first LDS store.
   bool tables_done = (dbg & 1) != 0;
   auto copy_all_tables = [&]() {
     if (SPARSE) {
-      copy_tables<C::TAB>(smem, a.tables_tf ? a.tables_tf : a.tables);
-      copy_tables<C::WS * (1 + C::DS) + 4>(smem + C::SP_WS, a.tables + (a.tables_tf ? a.off_ws : C::OFF_WS));
+      const float* tf = a.tables_tf ? a.tables_tf : a.tables;
+      const float* ws = a.tables + (a.tables_tf ? a.off_ws : C::OFF_WS);
+      // (only where a block has ONE tile -- the prologue is then paid per tile, per step in one-step launches: config #2
+      //  14.74 against 15.03 us per step.  A block that loops over tiles copies its tables once for many tiles, and
+      //  config #4 measured 7 % SLOWER with the batch, 2.12 against 1.98 ms per five-step launch: DESIGN 6)
+      if constexpr (GP::CT && GP::ONE) {
+        copy_tables_batched<C::TAB, C::WS * (1 + C::DS) + 4, GP::CT ? GP::TB : 64>(smem, tf, smem + C::SP_WS, ws);
+      } else {
+        copy_tables<C::TAB>(smem, tf, TB);
+        copy_tables<C::WS * (1 + C::DS) + 4>(smem + C::SP_WS, ws, TB);
+      }
     } else {
-      copy_tables<C::TABLES>(smem, a.tables);
+      copy_tables<C::TABLES>(smem, a.tables, TB);
     }
     tables_done = true;
   };
@@ -1660,6 +1770,17 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
         float y[4][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) { y[i][0] = cv[0]; y[i][1] = cv[1]; y[i][2] = cv[2]; y[i][3] = cv[3]; }
+        if constexpr (SPARSE) {
+          // the copies of c are made here, once, as register pairs: left to itself the compiler makes them on both
+          // sides of the first set-bit walk's entry test, twelve moves where six do
+#pragma unroll
+          for (int i = 1; i < 4; ++i)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              const floatx2 pr = opaque(floatx2{y[i][2 * h], y[i][2 * h + 1]});
+              y[i][2 * h] = pr[0]; y[i][2 * h + 1] = pr[1];
+            }
+        }
         if constexpr (!SPARSE) {
           // masks p0 .. p0+M+2 (padded row), then one float4 table row per
           // (filter column, 5-bit chunk) of each mask
@@ -1710,10 +1831,10 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
               }
 #pragma unroll
               for (int wi = 0; wi < NWORD; ++wi) {
-                unsigned long long w = 0ull;
-#pragma unroll
-                for (int t = 0; t < PPW; ++t)
-                  if (wi * PPW + t < NSLOT) w |= (unsigned long long)m[wi * PPW + t] << (t * C::K);
+                // (the halves of the word apart: 32-bit shift-ors; bit t*K + k keeps its place)
+                uint32_t lo = 0u, hi = 0u;
+                pack_masks<C::K, 0, PPW>(m + wi * PPW, NSLOT - wi * PPW, lo, hi);
+                const unsigned long long w = (unsigned long long)lo | ((unsigned long long)hi << 32);
                 topdown_bits<C>(w, tab, wi * PPW, y);
               }
             } else {
@@ -1738,12 +1859,10 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
         const Philox4 r = philox4x32(a.rng.seq_offset + (uint32_t)(n0 + nl), (uint32_t)pb,
                                         rng_word2(KIND_CHAIN_V, 0, 0, 0), a.rng.step + (uint32_t)st,
                                         a.rng.seed_lo, a.rng.seed_hi);
-        uint32_t byte = 0u;
+        uint32_t inv = 0u;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const uint32_t l = sample_letter(y[i][0], y[i][1], y[i][2], y[i][3], u01(r.v[i]));
-          byte |= (p0 + i < g.Lv() ? l : 0u) << (2 * i);
-        }
+        for (int i = 3; i >= 0; --i) inv = push_letter(inv, y[i][0], y[i][1], y[i][2], y[i][3], u01(r.v[i]));
+        const uint32_t byte = letter_byte<GP::WHOLE_BYTES>(inv, p0, g.Lv());
         reinterpret_cast<unsigned char*>(let + (size_t)nl * g.LWs())[pb] = (unsigned char)byte;
       }
       __syncthreads();
