@@ -7,7 +7,8 @@ behind the C-ABI in include/crbm_amd.h.
 from .crbm import CRBM  # noqa: F401
 from . import dist  # noqa: F401
 from .sequences import (seqsToCodes, codesToOneHot, seqToOneHot, readSeqsFromFasta,  # noqa: F401
-                        splitTrainingTest, fastaToCodes, writeFasta, load_sample, seqsToStream, fastaToStream, shuffleStream)
+                        splitTrainingTest, fastaToCodes, writeFasta, load_sample, seqsToStream, fastaToStream, shuffleStream,
+                        readVcf)
 from .calibrate import ScoreHistogram  # noqa: F401
 from .utils import saveMotifs, saveSites  # noqa: F401
 

@@ -688,6 +688,132 @@ class CRBM(object):
             out["dfe"][idx], out["per_motif"][idx], out["windows"][idx] = dfe, pm, win
         return out
 
+    @staticmethod
+    def _allele_strings(x, what, V):
+        """`what` (ref or alt of alleleEffects), a sequence of V strings, as (codes, offsets): the letters of all
+        alleles in one uint8 array (ACGT in either case 0..3, N 4, anything else 255) and the int64 offsets (V + 1) of
+        every allele in it; "", "-" and "." are empty"""
+        if isinstance(x, (str, bytes)) or not hasattr(x, "__len__"):
+            raise ValueError("%s must be a sequence of strings, one per variant" % what)
+        x = list(x)
+        if len(x) != V:
+            raise ValueError("%s must hold one entry per variant (%d), got %d" % (what, V, len(x)))
+        try:
+            text = "".join(x)                                        # (refuses what is no string)
+            if "-" in text or "." in text:
+                x = ["" if s == "-" or s == "." else s for s in x]
+                text = "".join(x)
+            off = np.zeros(V + 1, np.int64)
+            np.cumsum(np.fromiter(map(len, x), np.int64, V), out=off[1:])
+        except TypeError:
+            raise ValueError("%s must be a sequence of strings, one per variant" % what)
+        try:
+            raw = np.frombuffer(text.encode("latin-1"), dtype=np.uint8)
+        except UnicodeEncodeError:
+            raw = np.full(int(off[-1]), ord("?"), np.uint8)
+        lut = _LETTER_LUT.copy()
+        lut[ord("N")] = lut[ord("n")] = 4
+        return lut[raw], off
+
+    @staticmethod
+    def _segments(flat, start, length):
+        """the runs flat[start[i] : start[i] + length[i]] back to back, and their offsets (n + 1)"""
+        off = np.zeros(start.size + 1, np.int64)
+        np.cumsum(length, out=off[1:])
+        idx = np.repeat(start - off[:-1], length) + np.arange(int(off[-1]), dtype=np.int64)
+        return flat[idx], off
+
+    _ALLELE_MAX = 65535              # letters of a ref or an alt (crbm_allele_effects_codes)
+
+    def alleleEffects(self, stream, pos, ref, alt, offsets=None, seq=None, trim=True):
+        """variantEffects for alleles of any length -- insertions, deletions, block substitutions: dict of 'dfe' (V,)
+        float32, 'per_motif' (V, K) float32 and 'windows' (V, 2) int32.  Variant i replaces the len(ref[i]) letters
+        of the stream from pos[i] on by alt[i]; dfe[i] = F(edited stream) - F(stream) with the F of variantEffects,
+        per_motif[i, k] motif k's share of the hidden part (dfe = per_motif.sum(1) - (sum c[alt] - sum c[ref])),
+        windows[i] the valid windows of the reference and of the alternative haplotype around the variant.
+        `ref` and `alt`: sequences of strings, one per variant; ACGT in either case are letters, N in `ref` is code 4,
+        "", "-" and "." are empty (a pure insertion or deletion); any other letter in `alt` is refused.  `ref` is
+        always checked against the stream.  `pos`, `seq` and `offsets` as in variantEffects; pos + len(ref) must stay
+        inside the record (with `seq`) or the stream.  trim=True removes the longest common prefix of (ref, alt), then
+        the longest common suffix, and advances pos by the prefix: the anchor base of a VCF indel goes.  A variant
+        that trims to nothing, or whose replaced span holds a code 4, gives zeros.  sequences.readVcf reads the
+        arguments from a file.  The same models are refused as in scanSites."""
+        _, stream, offsets = self._scan_input(stream, 0.0, offsets)
+        pos = np.asarray(pos)
+        if pos.ndim != 1 or not (np.issubdtype(pos.dtype, np.integer) or pos.size == 0):
+            raise ValueError("pos must be a 1-D integer array")
+        pos = pos.astype(np.int64)
+        V = pos.size
+        rc, ro = self._allele_strings(ref, "ref", V)
+        ac, ao = self._allele_strings(alt, "alt", V)
+        if rc.size and int(rc.max()) > 4:
+            raise ValueError("ref must hold letters A, C, G, T or N")
+        if ac.size and int(ac.max()) > 3:
+            raise ValueError("alt must hold letters A, C, G, T")
+        R, A = np.diff(ro), np.diff(ao)
+        if seq is not None:
+            if offsets is None:
+                raise ValueError("seq needs the offsets of the records")
+            seq = np.asarray(seq)
+            if seq.shape != pos.shape or not (np.issubdtype(seq.dtype, np.integer) or seq.size == 0):
+                raise ValueError("seq must be an integer array with one record index per variant")
+            seq = seq.astype(np.int64)
+            if V and (seq.min() < 0 or seq.max() >= offsets.size - 1):
+                raise ValueError("seq must lie in [0, %d)" % (offsets.size - 1))
+            length = offsets[seq + 1] - 1 - offsets[seq]
+            bad = np.flatnonzero((pos < 0) | (pos + R > length))
+            if bad.size:
+                raise ValueError("pos outside its record at variants %s" % bad[:5].tolist())
+            pos = pos + offsets[seq]
+        bad = np.flatnonzero((pos < 0) | (pos + R > stream.size))
+        if bad.size:
+            raise ValueError("pos outside the stream at variants %s" % bad[:5].tolist())
+        owner = np.repeat(np.arange(V, dtype=np.int64), R)
+        at = np.repeat(pos - ro[:-1], R) + np.arange(rc.size, dtype=np.int64)      # the stream position of every ref letter
+        bad = np.unique(owner[rc != stream[at]])
+        if bad.size:
+            raise ValueError("ref does not match the stream at %d of %d variants, the first at indices %s (another assembly?)"
+                             % (bad.size, V, bad[:5].tolist()))
+        rs, as_ = ro[:-1].copy(), ao[:-1].copy()                                     # (start, length) of every allele in rc / ac
+        R, A = R.copy(), A.copy()
+        if trim:
+            # the common prefix, then the common suffix of what is left: one letter of every allele still in the running
+            # per round, so the rounds are as many as the longest common run
+            for back in (False, True):
+                n, run = np.minimum(R, A), np.zeros(V, np.int64)
+                act = np.flatnonzero(n > 0)
+                while act.size:
+                    at = R[act] - 1 - run[act] if back else run[act]
+                    bt = A[act] - 1 - run[act] if back else run[act]
+                    act = act[rc[rs[act] + at] == ac[as_[act] + bt]]
+                    run[act] += 1
+                    act = act[run[act] < n[act]]
+                if not back:
+                    rs += run; as_ += run; pos += run
+                R -= run; A -= run
+        bad = np.flatnonzero((R > self._ALLELE_MAX) | (A > self._ALLELE_MAX))
+        if bad.size:
+            raise ValueError("ref and alt hold at most %d letters each; longer at variants %s" % (self._ALLELE_MAX, bad[:5].tolist()))
+        gaps = np.concatenate([[0], np.cumsum(rc == 4)])
+        send = ((R > 0) | (A > 0)) & (gaps[rs + R] == gaps[rs])                      # the rest: zeros by definition
+        K = self.num_motifs
+        out = {"dfe": np.zeros(V, np.float32), "per_motif": np.zeros((V, K), np.float32), "windows": np.zeros((V, 2), np.int32)}
+        for lo, hi in self._scan_cuts(stream, offsets):
+            idx = np.flatnonzero(send & (pos >= lo) & (pos + R <= hi))
+            if idx.size == 0:
+                continue
+            piece = stream[lo:hi]
+            p = np.ascontiguousarray(pos[idx] - lo)
+            rl = np.ascontiguousarray(R[idx], np.int32)
+            codes, aoff = self._segments(ac, as_[idx], A[idx])
+            codes = np.ascontiguousarray(codes, np.uint8)
+            dfe, pm, win = np.empty(idx.size, np.float32), np.empty((idx.size, K), np.float32), np.empty((idx.size, 2), np.int32)
+            self._call("crbm_allele_effects_codes", piece.ctypes.data_as(_lib._U8P), piece.size, idx.size,
+                       p.ctypes.data_as(_lib._I64P), rl.ctypes.data_as(_lib._I32P), aoff.ctypes.data_as(_lib._I64P),
+                       codes.ctypes.data_as(_lib._U8P), fptr(dfe), fptr(pm), win.ctypes.data_as(_lib._I32P))
+            out["dfe"][idx], out["per_motif"][idx], out["windows"][idx] = dfe, pm, win
+        return out
+
     def motifBestSites(self, data):
         """The best site of every (sequence, motif): dict of 'start' (n,K) int32, 'strand' (n,K) int8 and
         'prob' (n,K) float32 -- the largest probability over positions and strands (motifSites' scores),

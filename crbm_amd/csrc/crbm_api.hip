@@ -2863,6 +2863,144 @@ int variant_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t
   return CRBM_OK;
 }
 
+// ---- allele effects (crbm_allele_effects_codes) ---------------------------------------------------------------------
+// variant_effects_any for alleles of any length: a two-stream sweep over the chunks of allele_plan (crbm_sweep.h), which
+// hold different numbers of variants -- run_slabs walks the chunks one at a time.  Everything that can be refused is
+// refused on the host before anything is launched.  Per chunk, on its set's stream: the host gathers both haplotypes of
+// every variant and their table entries (gather_haplotypes) into the set's host buffer, one copy takes them up;
+// scan_encode_kernel makes letters and validity plane, crbm_allele_effects leaves per_motif [cnt][K] (set.oa) and the
+// valid windows [cnt][2], allele_combine_kernel forms dfe (set.ob); the outputs asked for are copied straight into the
+// caller's arrays.  Every set owns what it writes, sized for the largest chunk before the sweep starts.
+// CRBM_ALLELE_TIMING=1: tools/bench_alleles.py.
+int allele_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t nvar, const int64_t* pos, const int32_t* ref_len,
+                       const int64_t* alt_off, const uint8_t* alt_codes, float* dfe, float* per_motif, int32_t* windows) {
+  StreamSweep sw{h, "crbm_allele_effects_codes"};
+  int rc = sw.admit(codes, T);
+  if (rc) return rc;
+  ARGCHK(dfe || per_motif || windows, "null argument: at least one output is required");
+  ARGCHK(nvar >= 0 && nvar <= (int64_t)INT32_MAX, "nvar must lie in [0, 2^31 - 1]");
+  if (nvar == 0) return CRBM_OK;
+  ARGCHK(pos && ref_len && alt_off, "null argument");
+  {
+    unsigned bad = 0;
+    for (int64_t i = 0; i < T; ++i) bad |= codes[i] > 4 ? 1u : 0u;
+    ARGCHK(!bad, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
+    ARGCHK(alt_off[0] == 0, "crbm_allele_effects_codes: alt_off must ascend from 0");
+    for (int64_t i = 0; i < nvar; ++i) {
+      const int64_t A = alt_off[i + 1] - alt_off[i];
+      bad |= (A < 0 ? 1u : 0u) | (A > 65535 ? 2u : 0u) | (ref_len[i] < 0 || ref_len[i] > 65535 ? 4u : 0u);
+      bad |= pos[i] < 0 || pos[i] > T || (ref_len[i] >= 0 && pos[i] + ref_len[i] > T) ? 8u : 0u;
+      if (bad & 1u) break;               // (what follows a descending offset is not to be trusted)
+    }
+    ARGCHK(!(bad & 1u), "crbm_allele_effects_codes: alt_off must ascend from 0");
+    ARGCHK(!(bad & 2u), "crbm_allele_effects_codes: an alt of more than 65535 letters");
+    ARGCHK(!(bad & 4u), "crbm_allele_effects_codes: every ref_len must lie in [0, 65535]");
+    ARGCHK(!(bad & 8u), "crbm_allele_effects_codes: every span [pos, pos + ref_len) must lie inside [0, T]");
+    const int64_t nalt = alt_off[nvar];
+    ARGCHK(alt_codes || nalt == 0, "null argument");
+    for (int64_t i = 0; i < nalt; ++i) bad |= alt_codes[i] > 3 ? 16u : 0u;
+    ARGCHK(!(bad & 16u), "crbm_allele_effects_codes: every alt code must be a letter code 0..3");
+  }
+  rc = sweep_begin(h);
+  if (rc) return rc;
+  const int M = sw.M, K = h->K, nslab = sw.nslab;
+  const AllelePlan ap = allele_plan((long)nvar, ref_len, alt_off, M, K, (size_t)env_int("CRBM_SLAB_BYTES", 256 << 20),
+                                    getenv("CRBM_SLAB_BYTES") != nullptr);
+  auto code_bytes = [](long n) { return ((size_t)n + 15) & ~(size_t)15; };         // the table follows the codes
+  std::vector<uint8_t> host[2];
+  for (int i = 0; i < ap.nsets; ++i) {                     // everything both streams write, at its size, before either starts
+    const SweepSet set = sweep_set(h, i);
+    host[i].resize(code_bytes(ap.max_codes) + (size_t)ap.max_cnt * sizeof(AlleleEntry));
+    HIPCHK(set.stage->ensure((host[i].size() + 3) / 4));
+    HIPCHK(set.letters->ensure((size_t)ap.full.letter_words));
+    HIPCHK(set.own->scan_valid.ensure((size_t)ap.full.valid_words));
+    HIPCHK(set.oa->ensure((size_t)ap.max_cnt * K));
+    HIPCHK(set.ob->ensure((size_t)ap.max_cnt));
+    HIPCHK(set.own->var_windows.ensure((size_t)2 * ap.max_cnt));
+  }
+  const bool timing = env_int("CRBM_ALLELE_TIMING", 0) != 0;
+  struct Events {                        // destroyed on every way out
+    hipEvent_t e[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    ~Events() {
+      for (auto& set : e)
+        for (hipEvent_t ev : set)
+          if (ev) (void)hipEventDestroy(ev);
+    }
+  } events;
+  auto& tev = events.e;
+  double device_ms = 0.0;
+  int chunks = 0;
+  if (timing)
+    for (int i = 0; i < 2; ++i)
+      for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
+  rc = run_slabs((int)ap.cuts.size() - 1, 1, 2,
+    [&](int, int si, int chunk, int) -> int {
+      const SweepSet set = sweep_set(h, si);
+      const int64_t start = ap.cuts[chunk];
+      const int cnt = (int)(ap.cuts[chunk + 1] - start);
+      uint8_t* hap = host[si].data();
+      // (the table's place does not depend on the codes gathered: sized from the plan's arithmetic, checked below)
+      long n = 0;
+      for (int i = 0; i < cnt; ++i) n += allele_codes(ref_len[start + i], alt_off[start + i + 1] - alt_off[start + i], M);
+      AlleleEntry* table = reinterpret_cast<AlleleEntry*>(hap + code_bytes(n));
+      const long wrote = gather_haplotypes(codes, T, pos + start, ref_len + start, alt_off + start, alt_codes, cnt, M, hap, table);
+      if (wrote != n || n > ap.max_codes || cnt > ap.max_cnt) return fail(h, CRBM_ERR_INVALID, "crbm_allele_effects_codes: a chunk outgrew its plan");
+      const size_t up = code_bytes(n) + (size_t)cnt * sizeof(AlleleEntry);
+      HIPCHK(hipMemcpyAsync(set.stage->p, hap, up, hipMemcpyHostToDevice, set.st));
+      if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
+      const ScanLayout l = scan_layout(n, n);
+      const unsigned char* staged = reinterpret_cast<const unsigned char*>(set.stage->p);
+      ScanEncodeArgs e;
+      e.codes = staged;
+      e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;   // (no code above 4: checked above)
+      e.n = n; e.valid_words = l.valid_words;
+      hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
+      HIPCHK(hipGetLastError());
+      AlleleArgs a{};
+      a.tables = h->big() ? h->d_slab_tables : h->d_tables;
+      a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
+      a.starts = (int32_t)n; a.tiles = l.tiles; a.table_stride = sw.kms->TABLES_ALL;
+      if (h->big()) a.plan = slab_plan(h);
+      else { a.plan.Ks = K; a.plan.K = K; a.plan.last_k0 = 0; }
+      a.table = reinterpret_cast<const AlleleEntry*>(staged + code_bytes(n));
+      a.per_motif = set.oa->p; a.windows = set.own->var_windows.p;
+      a.cnt = cnt; a.pad_ = 0;
+      // a wave per variant, four waves a block
+      const unsigned gx = (unsigned)std::max(1, std::min((cnt + 3) / 4, std::max(1, h->num_cu * 8 / nslab)));
+      HIPCHK(jit_launch(sw.kjk->allele_effects, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(*sw.kms), set.st));
+      if (dfe) {
+        AlleleCombineArgs c;
+        c.per_motif = set.oa->p; c.codes = staged; c.table = a.table; c.c = h->dc; c.dfe = set.ob->p;
+        c.cnt = cnt; c.K = K; c.M = M; c.pad_ = 0;
+        hipLaunchKernelGGL(allele_combine_kernel, dim3(grid_for(cnt, 256, h->num_cu * 8)), dim3(256), 0, set.st, c);
+        HIPCHK(hipGetLastError());
+      }
+      if (timing) HIPCHK(hipEventRecord(tev[si][1], set.st));
+      return CRBM_OK;
+    },
+    [&](int, int si, int chunk, int) -> int {
+      const SweepSet set = sweep_set(h, si);
+      const size_t at = (size_t)ap.cuts[chunk], cnt = (size_t)(ap.cuts[chunk + 1] - ap.cuts[chunk]);
+      if (dfe) HIPCHK(hipMemcpyAsync(dfe + at, set.ob->p, cnt * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      if (per_motif) HIPCHK(hipMemcpyAsync(per_motif + at * K, set.oa->p, cnt * K * sizeof(float), hipMemcpyDeviceToHost, set.st));
+      if (windows) HIPCHK(hipMemcpyAsync(windows + 2 * at, set.own->var_windows.p, 2 * cnt * sizeof(int32_t), hipMemcpyDeviceToHost, set.st));
+      HIPCHK(hipStreamSynchronize(set.st));
+      if (timing) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, tev[si][0], tev[si][1]));
+        device_ms += ms;
+        ++chunks;
+      }
+      return CRBM_OK;
+    },
+    [&] { sweep_drain(h); });
+  if (rc) return rc;
+  if (timing) fprintf(stderr, "crbm_allele_effects_codes: kernels %.3f ms over %d chunks\n", device_ms, chunks);
+  HIPCHK(hipStreamSynchronize(h->stream2));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return CRBM_OK;
+}
+
 // ---- in-silico mutagenesis (crbm_mutagenesis*) ----------------------------------------------------------------------
 // dF (n,L,A) and / or pll (n) over a source, a two-stream sweep.  Specialised models without pooling: the fused
 // crbm_mutagenesis pass (mutagenesis_body; as many waves per block as the LDS holds accumulators beside the tables).
@@ -3123,6 +3261,13 @@ int crbm_variant_effects_codes(crbm_handle* h, const uint8_t* codes, int64_t T, 
                                const uint8_t* alt, float* dfe, float* dfe_per_motif, int32_t* windows) {
   ENTER();
   return variant_effects_any(h, codes, T, nvar, pos, alt, dfe, dfe_per_motif, windows);
+}
+
+int crbm_allele_effects_codes(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t nvar, const int64_t* pos,
+                              const int32_t* ref_len, const int64_t* alt_off, const uint8_t* alt_codes, float* dfe,
+                              float* dfe_per_motif, int32_t* windows) {
+  ENTER();
+  return allele_effects_any(h, codes, T, nvar, pos, ref_len, alt_off, alt_codes, dfe, dfe_per_motif, windows);
 }
 
 int crbm_mutagenesis(crbm_handle* h, const float* v, int32_t n, int32_t L, float* dfe, float* pll) {

@@ -3476,6 +3476,97 @@ __device__ void variant_effects_body(const VariantArgs& a) {
   }
 }
 
+// ===========================================================================
+// Allele effects (crbm_allele_effects_codes): what replacing R codes of a stream by A letters -- an insertion, a
+// deletion, a block substitution -- changes in its free energy, per motif.  The host stages both haplotypes of every
+// variant of a chunk back to back (crbm_sweep.h, gather_haplotypes; crbm_layout.h, AlleleEntry) and
+// scan_encode_kernel makes letters and validity plane of them.  refhap has R + M - 1 window starts from `off` on,
+// althap A + M - 1 from off + R + 2M - 2 on: the last window of a haplotype ends on its last code, so none reaches into
+// a neighbour.  The number of windows differs from variant to variant (M - 1 .. 65535 + M - 1), so a WAVE owns a
+// variant: lane l takes windows l, l + 64, ... of a haplotype in ascending order, + strand before -, z as
+// free_energy_body gathers it (conv_gather_quads per strand, strand <= DS), softplus added into the lane's registers
+// for NQW motif quads at a time (the outer loop); wave_sum adds the 64 lanes in its fixed tree; lane 0 writes
+// S_ref - S_alt = -(S_alt - S_ref).  Lane assignment and tree depend on the variant alone: no atomics, no LDS
+// accumulator, the same bits for every chunk, place in the list and launch geometry.  A `zero` variant scores nothing
+// and gets zeros.  blockIdx.y is the slab of a generic DNA model, which writes its own columns; slab 0 writes the valid
+// windows [cnt][2].  allele_combine_kernel (below, model-independent) forms dfe.
+// ===========================================================================
+struct AlleleArgs : ScanInput {          // starts = staged codes (unused), tiles unused
+  const AlleleEntry* table;              // [cnt]
+  float* per_motif;                      // [cnt][K]
+  int32_t* windows;                      // [cnt][2]
+  int32_t cnt;
+  int32_t pad_;
+};
+
+template <class C>
+__device__ void allele_effects_body(const AlleleArgs& a) {
+  if constexpr (C::POOL == 1) {       // refused on the host, as the scan
+    constexpr int K = C::K, M = C::M;
+    constexpr int NQW = C::NQ < 4 ? C::NQ : 4, NV = 4 * NQW;
+    HIP_DYNAMIC_SHARED(float, smem);
+    float* Tf = smem;
+    const ScanInput& in = a;
+    const int y = (int)blockIdx.y;
+    const SlabSpan span = slab_span<C>(in.plan, y);
+    copy_tables<C::TAB>(Tf, in.tables + (size_t)y * in.table_stride + C::OFF_TF);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    // sum[] = the wave's softplus sums of motifs [4 q0, 4 q0 + NV) over the valid ones of the n windows from `off` on;
+    // returns their number (all lanes call it: wave-uniform trip counts)
+    auto hap_sums = [&](int off, int n, int q0, float (&sum)[NV]) -> int {
+      float acc[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) acc[j] = 0.f;
+      int nwin = 0;
+#pragma unroll 1
+      for (int w0 = 0; w0 < n; w0 += 64) {
+        const int w = w0 + lane;
+        const bool ok = w < n && window_valid<M>(in.valid, off + w);
+        nwin += __popcll(__ballot(ok));
+        if (ok) {
+          const LetterWin<M> fwd = letter_window<M>(in.letters, off + w);
+#pragma unroll 1
+          for (int strand = 0; strand <= C::DS; ++strand) {
+            float z[NV];
+            conv_gather_quads<C, NQW>(Tf, strand ? revcomp_window<M>(fwd) : fwd, q0, z);
+#pragma unroll
+            for (int j = 0; j < NV; ++j)
+              if (4 * q0 + j < K) acc[j] += softplus_of_z(z[j]);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NV; ++j) sum[j] = wave_sum(acc[j]);
+      return nwin;
+    };
+    for (int v = blockIdx.x * nwaves + wave; v < a.cnt; v += gridDim.x * nwaves) {
+      const AlleleEntry e = a.table[v];
+      const int n0 = e.zero ? 0 : e.R + M - 1, n1 = e.zero ? 0 : e.A + M - 1;
+      const int off1 = e.off + e.R + 2 * (M - 1);
+      float* out = a.per_motif + (size_t)v * in.plan.K + span.k0;
+      int nwin0 = 0, nwin1 = 0;
+#pragma unroll 1
+      for (int q0 = 0; q0 < C::NQ; q0 += NQW) {
+        float sref[NV], salt[NV];
+        nwin0 = hap_sums(e.off, n0, q0, sref);
+        nwin1 = hap_sums(off1, n1, q0, salt);
+        if (lane == 0) {
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            const int kk = 4 * q0 + j;
+            if (kk >= span.kskip && kk < span.kend) out[kk] = sref[j] - salt[j];
+          }
+        }
+      }
+      if (lane == 0 && y == 0) {
+        a.windows[2 * (size_t)v] = nwin0;
+        a.windows[2 * (size_t)v + 1] = nwin1;
+      }
+    }
+  }
+}
+
 #ifdef CRBM_DEFINE_MISC_KERNELS
 // ===========================================================================
 // Model-independent kernels, compiled ahead of time into libcrbm_hip.so.
@@ -3701,6 +3792,34 @@ __global__ void __launch_bounds__(256) variant_combine_kernel(VariantCombineArgs
     float s = 0.f;
     for (int k = 0; k < a.K; ++k) s += row[k];
     a.dfe[i] = ref < 4u ? s - (a.c[a.alt[i] & 3u] - a.c[ref]) : 0.f;
+  }
+}
+
+// The tail of the allele effects (allele_effects_body), variant_combine_kernel's rule for alleles of any length:
+// dfe[i] = sum_k per_motif[i][k] - (sum_j c[alt_j] - sum_j c[ref_j]), the motifs added in ascending k, the bias sums
+// in ascending letter order, ref and alt separately; exactly 0 for a `zero` variant (its row is all zeros).  The ref
+// letters are codes [M - 1, M - 1 + R) of the staged refhap, the alt letters codes [M - 1, M - 1 + A) of the althap.
+struct AlleleCombineArgs {
+  const float* per_motif;       // [cnt][K]
+  const unsigned char* codes;   // the staged haplotypes
+  const AlleleEntry* table;     // [cnt]
+  const float* c;               // (4) the visible bias
+  float* dfe;                   // [cnt]
+  int32_t cnt, K, M, pad_;
+};
+__global__ void __launch_bounds__(256) allele_combine_kernel(AlleleCombineArgs a) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.cnt; i += gridDim.x * blockDim.x) {
+    const AlleleEntry e = a.table[i];
+    if (e.zero) { a.dfe[i] = 0.f; continue; }
+    const float* row = a.per_motif + (size_t)i * a.K;
+    float s = 0.f;
+    for (int k = 0; k < a.K; ++k) s += row[k];
+    const unsigned char* ref = a.codes + e.off + a.M - 1;
+    const unsigned char* alt = ref + e.R + 2 * (a.M - 1);
+    float cr = 0.f, ca = 0.f;
+    for (int j = 0; j < e.R; ++j) cr += a.c[ref[j] & 3u];
+    for (int j = 0; j < e.A; ++j) ca += a.c[alt[j] & 3u];
+    a.dfe[i] = s - (ca - cr);
   }
 }
 

@@ -59,6 +59,14 @@ inline ScanLayout scan_layout(long n, long starts) {
   s.tiles = (int)((starts + 63) / 64);
   return s;
 }
+// Allele effects (crbm_kernels.h, allele_effects_body): one entry per variant of a chunk.  The variant's two haplotypes
+// stand back to back in the chunk's staged codes: refhap = left . ref . right, R + 2M - 2 codes from `off`, then althap =
+// left . alt . right, A + 2M - 2 codes (crbm_sweep.h, gather_haplotypes).  zero: R = A = 0, or the replaced span holds a
+// code 4 -- every output of the variant is 0 by definition.
+struct AlleleEntry {
+  int32_t off, R, A, zero;
+};
+inline long allele_codes(long R, long A, int M) { return R + A + 4L * (M - 1); }
 // Score histogram (crbm_kernels.h, scan_hist_body): the 32-bit counters of `gq` motif quads, [4 gq][S][nbins], `copies`
 // times, and one word for the valid windows stand behind the gather table (tab_bytes) in at most 160 KB of LDS.  gq is
 // all NQ quads when they fit, else the largest multiple of the gather's four quads that does, else what fits (the

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "crbm_layout.h"
 
@@ -94,6 +95,76 @@ inline void gather_contexts(const uint8_t* codes, int64_t T, const int64_t* pos,
     else
       for (int j = 0; j < CW; ++j) dst[j] = lo + j >= 0 && lo + j < T ? codes[lo + j] : (uint8_t)4;
   }
+}
+
+// The chunks of an allele sweep (crbm_api.hip, allele_effects_any): variant i replaces ref_len[i] codes by the
+// alt_off[i + 1] - alt_off[i] letters of its alt.  It costs its staged haplotypes, n_i = R + A + 4M - 4 codes (no
+// separators: the kernel bounds the window starts of a haplotype), their letter and validity bits (3 bits each, rounded
+// up per variant), its table entry and the outputs 4 (K + 3) out of `budget` (CRBM_SLAB_BYTES, or 256 MB); unless the
+// budget was set by hand a chunk stays within 32 MB.  Chunk j is variants [cuts[j], cuts[j + 1]): the longest prefix of
+// what is left that stays within the budget and within 2^30 staged codes (the kernels' window starts are 32 bits wide),
+// and at least one variant.  Two buffer sets exactly when there is more than one chunk; every set is sized for the
+// longest chunk (max_cnt variants) and for the most staged codes (max_codes), `full` being the layout of the latter.
+struct AllelePlan {
+  std::vector<int64_t> cuts;
+  int nsets, max_cnt;
+  long max_codes;
+  ScanLayout full;
+};
+inline size_t allele_cost(long R, long A, int M, int K) {
+  const size_t n = (size_t)allele_codes(R, A, M);
+  return n + (3 * n + 7) / 8 + sizeof(AlleleEntry) + (size_t)4 * (K + 3);
+}
+inline AllelePlan allele_plan(long nvar, const int32_t* ref_len, const int64_t* alt_off, int M, int K, size_t budget, bool budget_was_set) {
+  AllelePlan p;
+  if (!budget_was_set) budget = std::min(budget, (size_t)32 << 20);
+  p.cuts.push_back(0);
+  p.max_cnt = 0; p.max_codes = 0;
+  size_t bytes = 0;
+  long codes = 0;
+  for (long i = 0; i < nvar; ++i) {
+    const long R = ref_len[i], A = (long)(alt_off[i + 1] - alt_off[i]), n = allele_codes(R, A, M);
+    const size_t cost = allele_cost(R, A, M, K);
+    if (i > p.cuts.back() && (bytes + cost > budget || codes + n > (1L << 30))) {
+      p.cuts.push_back(i);
+      bytes = 0; codes = 0;
+    }
+    bytes += cost; codes += n;
+    p.max_cnt = std::max(p.max_cnt, (int)(i + 1 - p.cuts.back()));
+    p.max_codes = std::max(p.max_codes, codes);
+  }
+  p.cuts.push_back(nvar);
+  p.nsets = p.cuts.size() > 2 ? 2 : 1;
+  p.full = scan_layout(p.max_codes, p.max_codes);
+  return p;
+}
+// the haplotypes of variants [0, cnt) of a stream of T codes, back to back at dst, and their table entries: per variant
+// left = codes [pos - M + 1, pos), the R replaced codes, right = codes [pos + R, pos + R + M - 1), then left, the A alt
+// letters and right again; code 4 (no letter) for what lies outside the stream.  0 <= pos, pos + R <= T.  Returns the
+// number of codes written.
+inline long gather_haplotypes(const uint8_t* codes, int64_t T, const int64_t* pos, const int32_t* ref_len, const int64_t* alt_off,
+                              const uint8_t* alt_codes, int cnt, int M, uint8_t* dst, AlleleEntry* table) {
+  auto span = [&](uint8_t* d, int64_t lo, int64_t n) {       // codes [lo, lo + n), 4 outside the stream
+    if (lo >= 0 && lo + n <= T) { if (n) memcpy(d, codes + lo, (size_t)n); }
+    else
+      for (int64_t j = 0; j < n; ++j) d[j] = lo + j >= 0 && lo + j < T ? codes[lo + j] : (uint8_t)4;
+  };
+  long at = 0;
+  for (int i = 0; i < cnt; ++i) {
+    const int64_t p = pos[i];
+    const int R = ref_len[i], A = (int)(alt_off[i + 1] - alt_off[i]);
+    AlleleEntry e{(int32_t)at, R, A, R == 0 && A == 0 ? 1 : 0};
+    uint8_t* d = dst + at;
+    span(d, p - (M - 1), (int64_t)R + 2 * (M - 1));          // left . ref . right is one run of the stream
+    for (int j = 0; j < R; ++j) e.zero |= d[M - 1 + j] > 3 ? 1 : 0;
+    d += R + 2 * (M - 1);
+    memcpy(d, dst + at, (size_t)(M - 1));
+    if (A) memcpy(d + M - 1, alt_codes + alt_off[i], (size_t)A);
+    memcpy(d + M - 1 + A, dst + at + M - 1 + R, (size_t)(M - 1));
+    at += allele_codes(R, A, M);
+    table[i] = e;
+  }
+  return at;
 }
 
 }  // namespace crbm

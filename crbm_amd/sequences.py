@@ -198,6 +198,41 @@ def fastaToStream(filename):
     return seqsToStream(seqs, ids)
 
 
+def readVcf(path, names):
+    """The variants of a VCF file for CRBM.alleleEffects: dict of `seq` (int64, the index of CHROM in `names`, as
+    fastaToStream returns them), `pos` (int64, 0-based), `ref` and `alt` (lists of strings), `line` (int64, the
+    1-based line of the file a variant came from) and `skipped`, the counts of what was left out: 'symbolic' alleles
+    (<...>, * and .), 'breakend' alleles ([ or ]) and records on 'unknown_contig's.  Plain text or .gz; # lines are
+    skipped; a multi-allelic ALT gives one variant per allele.  INFO and FORMAT are not read."""
+    import gzip
+    index = {str(n): i for i, n in enumerate(names)}
+    seq, pos, ref, alt, line = [], [], [], [], []
+    skipped = {"symbolic": 0, "breakend": 0, "unknown_contig": 0}
+    opener = gzip.open if str(path).endswith(".gz") else open
+    with opener(path, "rt") as f:
+        for no, text in enumerate(f, 1):
+            if text.startswith("#") or not text.strip():
+                continue
+            cols = text.rstrip("\r\n").split("\t")
+            if len(cols) < 5:
+                raise ValueError("%s line %d: a VCF record has at least five tab-separated columns" % (path, no))
+            try:
+                p = int(cols[1]) - 1
+            except ValueError:
+                raise ValueError("%s line %d: POS is not an integer" % (path, no))
+            for a in cols[4].split(","):
+                if "[" in a or "]" in a:
+                    skipped["breakend"] += 1
+                elif a.startswith("<") or a in ("*", ".", ""):
+                    skipped["symbolic"] += 1
+                elif cols[0] not in index:
+                    skipped["unknown_contig"] += 1
+                else:
+                    seq.append(index[cols[0]]); pos.append(p); ref.append(cols[3]); alt.append(a); line.append(no)
+    return {"seq": np.array(seq, np.int64), "pos": np.array(pos, np.int64), "ref": ref, "alt": alt,
+            "line": np.array(line, np.int64), "skipped": skipped}
+
+
 def shuffleStream(stream, seed):
     """The background of a stream for CRBM.scoreHistogram: the letters of every maximal run of letters (codes 0..3)
     permuted uniformly at random, every code 4 -- gaps and record separators -- where it was.  Each run, and with it

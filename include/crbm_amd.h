@@ -290,6 +290,37 @@ int crbm_scan_histogram_codes(crbm_handle* h, const uint8_t* codes, int64_t T, f
 int crbm_variant_effects_codes(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t nvar, const int64_t* pos,
                                const uint8_t* alt, float* dfe, float* dfe_per_motif, int32_t* windows);
 
+/* ---- allele effects: insertions, deletions and block substitutions -------------------
+ * crbm_variant_effects_codes for alleles of any length.  Stream, codes and window validity as crbm_scan_sites_codes.
+ * Variant i = (pos_i, R_i, alt_i[0..A_i)) replaces the R_i codes codes[pos_i .. pos_i+R_i) with the A_i letters
+ * alt_codes[alt_off[i] .. alt_off[i+1]).  R = 0: a pure insertion in front of pos; A = 0: a pure deletion;
+ * R = A = 1: the SNP.  Two haplotype contexts are built per variant, with left = codes [pos-M+1, pos) and
+ * right = codes [pos+R, pos+R+M-1), positions outside the stream reading as code 4:
+ *   refhap = left . codes[pos..pos+R) . right      R+M-1 window starts
+ *   althap = left . alt . right                    A+M-1 window starts
+ * A window is valid when all its M codes are letters.  With x as crbm_variant_effects_codes documents F (the
+ * activations of crbm_free_energy per strand, not the scan's site score):
+ *   S_hap,k            = sum over the valid windows of hap and the strands of softplus(x_k)
+ *   dfe_per_motif[i,k] = -(S_alt,k - S_ref,k)                                                     (nvar,K) fp32
+ *   dfe[i]             = sum_k dfe_per_motif[i,k] (ascending k) - (sum_j c[alt_j] - sum_j c[ref_j])   (nvar) fp32
+ *   windows[i][0..1]   = the valid windows of refhap (0..R+M-1) and of althap (0..A+M-1)          (nvar,2) int32
+ * dfe equals F(edited stream) - F(stream) over the whole stream: every other window is the same in both.
+ * Exact zeros (dfe 0, the per_motif row 0, windows 0,0): R = A = 0, and a replaced span that holds a code 4 (the SNP
+ * rule for a variant on an N).  A variant with no valid window on either haplotype gives a zero per_motif row and
+ * the bias term alone.  Limits: R and A at most 65535 each; 0 <= pos and pos + R <= T (pos = T is allowed with
+ * R = 0); alt codes 0..3; alt_off holds nvar+1 entries ascending from 0.
+ * Every output of a variant depends on that variant's staged codes alone: the same bits in every run, for every
+ * CRBM_SLAB_BYTES (the list goes through the device in chunks of R + A + 4M - 4 staged codes per variant), for every
+ * launch geometry and under any permutation or duplication of the list.  Any of the three outputs may be NULL;
+ * nvar == 0 succeeds and writes nothing.  Served: exactly the models crbm_scan_sites_codes serves.
+ * CRBM_ERR_INVALID: what crbm_variant_effects_codes refuses, and a ref_len outside [0, 65535], an alt_off that does
+ * not ascend from 0, an alt of more than 65535 letters, an alt code above 3, a span outside the stream -- all found on
+ * the host before anything is launched: the outputs are left as they were.  The handle stays usable. */
+int crbm_allele_effects_codes(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t nvar,
+                              const int64_t* pos, const int32_t* ref_len,
+                              const int64_t* alt_off /* nvar+1, ascending from 0 */, const uint8_t* alt_codes,
+                              float* dfe, float* dfe_per_motif, int32_t* windows);
+
 /* ---- in-silico mutagenesis and pseudo-log-likelihood -----------------------------
  * WHICH bases matter.  With F(v) = L * crbm_free_energy(v), the unnormalised free energy of one sequence (derived from
  * theano_freeEnergyForData, convRBM.py:657-676: the hidden terms of all motifs and strands, pooled form when
