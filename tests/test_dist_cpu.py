@@ -226,6 +226,14 @@ def test_wire_format_round_trip_and_rejects_garbage():
     assert back["motifs"].dtype == np.float32 and back["motifs"].flags.writeable
     np.testing.assert_array_equal(back["bits"][0], state["bits"][0])
     assert back["bits"][1] is None and back["list"] == state["list"] and back["empty"].shape == (0, 3)
+    # 64-bit seeds: below 2^63 in the fixed-width form, from 2^63 on (bit 63 set) in the b"I" branch -- unchanged either way
+    for seed in (0x9E3779B900000005, 2**64 - 1, 2**63, 2**63 - 1, 2**32 - 2, -(2**63) - 1):
+        from crbm_amd.dist import _enc
+        one = []
+        _enc(seed, one)
+        assert one[0][:1] == (b"i" if -(2**63) <= seed < 2**63 else b"I")
+        back_rng = decode(encode({"rng": (seed, 2**32 - 2, 2**31)}))["rng"]
+        assert back_rng == (seed, 2**32 - 2, 2**31) and all(type(x) is int for x in back_rng)
     with pytest.raises(TypeError):
         encode({"f": lambda: 0})
     with pytest.raises(TypeError):

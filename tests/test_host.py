@@ -241,6 +241,48 @@ def test_load_state_defers_device_state(tmp_path):
     assert [g for g in got if g[0] == "r"][0][1] == (77, 5, 1)
 
 
+def test_state_files_keep_a_64_bit_seed_and_high_counters(tmp_path, monkeypatch):
+    """saveState / loadState with a seed whose bit 63 is set and step counters of 2^31 and beyond: the file holds them,
+    loadState hands exactly them to set_rng, and the handle's configuration and crbm_set_rng get the seed as an unsigned
+    64-bit value.  (saveModel writes the reference's tuple, which has neither seed nor counters: loadModel of such a
+    model gives a model with a seed of its own, as the reference does.)"""
+    import ctypes
+    import joblib
+    from crbm_amd import CRBM
+    SEED_HI, gstep, estep = 0x9E3779B900000005, 2**31 + 5, 2**32 - 1
+    K, M, B, Lf = 3, 4, 8, 16
+    a = CRBM(K, M, batchsize=B, fantasy_hidden_len=Lf, seed=SEED_HI)
+    assert a.seed == SEED_HI
+    fh = np.random.default_rng(0).binomial(1, 0.2, size=(B, K, 1, Lf)).astype(np.float32)
+    state = {"velocities": (np.zeros((K, 1, 4, M), np.float32), np.zeros((1, K), np.float32), np.zeros((1, 4), np.float32)),
+             "fantasy_bits": (np.packbits(fh.astype(np.uint8), axis=3),) * 2, "fantasy_hidden_len": Lf, "world_size": 1,
+             "rng": (SEED_HI, gstep, estep)}
+    monkeypatch.setattr(a, "_full_state", lambda: state)          # what a handle reports (crbm_get_rng: c_uint64, c_uint32 x 2)
+    fn = str(tmp_path / "s.pkl")
+    a.saveState(fn)
+    assert joblib.load(fn)[2]["rng"] == (SEED_HI, gstep, estep)
+    b = CRBM.loadState(fn)
+    assert b.seed == SEED_HI and b._handle is None and b._pending_state["rng"] == (SEED_HI, gstep, estep)
+    calls = []
+    b._handle, b._lib = object(), None                             # no GPU here: record what reaches the library
+    monkeypatch.setattr(b, "_call", lambda name, *args: calls.append((name, args)))
+    b._install_state(b._pending_state)
+    assert ("crbm_set_rng", (SEED_HI, gstep, estep)) in calls
+    b.set_rng(-1 & 0xFFFFFFFFFFFFFFFF, gstep, estep)                # 2^64 - 1 passes as it is
+    assert calls[-1] == ("crbm_set_rng", (2**64 - 1, gstep, estep)) and b.seed == 2**64 - 1
+    b._handle = None
+    # the binding declares the ABI's widths: seed 64 bits, counters 32 bits, all unsigned
+    from crbm_amd._lib import SIGNATURES, CrbmConfig
+    assert SIGNATURES["crbm_set_rng"][1][1:] == [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]
+    assert SIGNATURES["crbm_get_rng"][1][1:] == [ctypes.POINTER(t) for t in (ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32)]
+    assert dict(CrbmConfig._fields_)["seed"] is ctypes.c_uint64
+    fm = str(tmp_path / "m.pkl")
+    a.saveModel(fm)
+    c = CRBM.loadModel(fm)
+    np.testing.assert_array_equal(c.motifs.get_value(), a.motifs.get_value())
+    assert len(joblib.load(fm)) == 2                                # the reference's (numpyParams, hyperparams): no sampler state
+
+
 def test_bench_line_contract_of_the_tracked_profile():
     """The bench line the round's evidence holds (profiles/r04_bench_cfg2.json, written by `python bench.py --full` on an
     MI355X): the driver's keys, BASELINE.json's metric and config, a roofline object that names the resource that

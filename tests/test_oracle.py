@@ -67,6 +67,53 @@ def test_uniform_layout():
     assert np.array_equal(u.astype(np.float32).astype(np.float64), u)
 
 
+def test_every_counter_word_changes_the_uniforms():
+    """The seed's high word, the step, the index, the strand, the kind and the group each change the uniforms; the step
+    and the index are uint32 words: periodic with 2^32 (what tests/test_gpu_rng_counters.py compares the kernels with
+    at steps and indices that cross 2^16, 2^31 and 2^32)."""
+    SEED_HI = 0x9E3779B900000005
+    idx = np.array([2**16 - 3, 2**31 - 3, 2**32 - 3]) + np.arange(6)[:, None]           # (6, 3): batches across each power
+    idx = idx.T.ravel()
+    base_h = hidden_uniforms(SEED_HI, 2**32 - 2, idx, K=25, Lh=7, strand=0, kind=1)
+    base_v = visible_uniforms(SEED_HI, 2**32 - 2, idx, L=13, kind=2)
+    same = lambda a, b: np.array_equal(a, b)
+    # the high key word: neither dropped nor replaced by the low one
+    for seed in (5, 5 | (5 << 32), SEED_HI ^ (1 << 63), SEED_HI ^ (1 << 32)):
+        assert not same(hidden_uniforms(seed, 2**32 - 2, idx, 25, 7, 0, 1), base_h)
+        assert not same(visible_uniforms(seed, 2**32 - 2, idx, 13, 2), base_v)
+    # the key words are ordered: (lo, hi) is not (hi, lo)
+    swapped = ((SEED_HI & 0xFFFFFFFF) << 32) | (SEED_HI >> 32)
+    assert not same(hidden_uniforms(swapped, 2**32 - 2, idx, 25, 7, 0, 1), base_h)
+    for step in (2**32 - 1, 2**31 - 2, 2**16 - 2, 0):
+        assert not same(hidden_uniforms(SEED_HI, step, idx, 25, 7, 0, 1), base_h)
+        assert not same(visible_uniforms(SEED_HI, step, idx, 13, 2), base_v)
+    for shift in (1, 2**16, 2**31):
+        assert not same(hidden_uniforms(SEED_HI, 2**32 - 2, idx + shift, 25, 7, 0, 1), base_h)
+        assert not same(visible_uniforms(SEED_HI, 2**32 - 2, idx + shift, 13, 2), base_v)
+    assert not same(hidden_uniforms(SEED_HI, 2**32 - 2, idx, 25, 7, 1, 1), base_h)       # strand
+    for kind in (3, 4, 6):
+        assert not same(hidden_uniforms(SEED_HI, 2**32 - 2, idx, 25, 7, 0, kind), base_h)
+    for kind in (5, 7):
+        assert not same(visible_uniforms(SEED_HI, 2**32 - 2, idx, 13, kind), base_v)
+    g = base_h[:, :20, 0, :].reshape(len(idx), 2, 10, 7)                                 # groups of ten units
+    assert not same(g[:, 0], g[:, 1]) and not same(base_h[:, 20:25, 0], base_h[:, 0:5, 0])
+    # periodic with 2^32 in the step and in the index, and only with 2^32
+    assert same(hidden_uniforms(SEED_HI, 2**33 - 2, idx, 25, 7, 0, 1), base_h)
+    assert same(visible_uniforms(SEED_HI, -2, idx, 13, 2), base_v)
+    assert same(hidden_uniforms(SEED_HI, 2**32 - 2, idx + 2**32, 25, 7, 0, 1), base_h)
+    assert same(visible_uniforms(SEED_HI, 2**32 - 2, idx % 2**32, 13, 2), base_v)
+    # ... and the chain of an OracleCRBM takes them from seed, gibbs_step and seq_offset
+    o = OracleCRBM(3, 4, doublestranded=True, batchsize=6, fantasy_hidden_len=9, seed=SEED_HI)
+    o.b = o.b + 5.0
+    o.gibbs_step, o.seq_offset = 2**32 - 2, 2**32 - 3
+    o.gibbs_steps(3)
+    p = OracleCRBM(3, 4, doublestranded=True, batchsize=6, fantasy_hidden_len=9, seed=SEED_HI, W=o.W)
+    p.b = o.b
+    p.gibbs_step, p.seq_offset = -2, -3
+    p.gibbs_steps(3)
+    assert same(o.fantasy_h, p.fantasy_h) and same(o.last_v_model, p.last_v_model) and o.fantasy_h.sum() > 0
+
+
 # --------------------------------------------------------------------------
 # bottom-up: reference tests/testcrbm.py:154-200
 # --------------------------------------------------------------------------
