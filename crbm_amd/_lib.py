@@ -120,6 +120,7 @@ SIGNATURES = {
     "crbm_motif_sites_resident": (_I32, [_H, _I32, _I32] + _SITES_TAIL),
     "crbm_scan_sites_codes": (_I32, [_H, _U8P, _I64, ctypes.c_float, _I64, _SITEP, _I64P]),
     "crbm_scan_histogram_codes": (_I32, [_H, _U8P, _I64, ctypes.c_float, ctypes.c_float, _I32, ctypes.POINTER(_U64), _I64P]),
+    "crbm_scan_records_codes": (_I32, [_H, _U8P, _I64, _I64P, _I64, _I64P, _I64P, _F, _F, _I32P, _I32P, _F, ctypes.POINTER(ctypes.c_double)]),
     "crbm_variant_effects_codes": (_I32, [_H, _U8P, _I64, _I64, _I64P, _U8P, _F, _F, _I32P]),
     "crbm_allele_effects_codes": (_I32, [_H, _U8P, _I64, _I64, _I64P, _I32P, _I64P, _U8P, _F, _F, _I32P]),
     "crbm_mutagenesis": (_I32, [_H, _F, _I32, _I32, _F, _F]),

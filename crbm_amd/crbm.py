@@ -607,6 +607,70 @@ class CRBM(object):
             windows += w
         return ScoreHistogram(counts, np.linspace(lo, hi, int(bins) + 1), windows, self.doublestranded)
 
+    def _records_call(self, stream, rec_start):
+        """crbm_scan_records_codes over one piece (at most _SCAN_MAX letters, accumulators within the slab budget):
+        the dict of recordSummary for its records"""
+        R, K = rec_start.size - 1, self.num_motifs
+        out = {"windows": np.zeros(R, np.int64), "letters": np.zeros((R, 4), np.int64),
+               "per_motif": np.zeros((R, K), np.float32), "fe": np.zeros(R, np.float32),
+               "start": np.full((R, K), -1, np.int32), "strand": np.zeros((R, K), np.int32),
+               "prob": np.zeros((R, K), np.float32)}
+        unit = ctypes.c_double(0.0)
+        self._call("crbm_scan_records_codes", stream.ctypes.data_as(_lib._U8P), stream.size,
+                   rec_start.ctypes.data_as(_lib._I64P), R, out["windows"].ctypes.data_as(_lib._I64P),
+                   out["letters"].ctypes.data_as(_lib._I64P), fptr(out["fe"]), fptr(out["per_motif"]),
+                   out["start"].ctypes.data_as(_lib._I32P), out["strand"].ctypes.data_as(_lib._I32P), fptr(out["prob"]),
+                   ctypes.byref(unit))
+        out["unit"] = unit.value
+        return out
+
+    def _records_cuts(self, stream, offsets):
+        """[r0, r1) of the records of the pieces a stream is summarised in: _scan_cuts' pieces of at most _SCAN_MAX
+        letters, cut again so that the device accumulators of a piece, records * (16 K + 40) bytes (sums and keys per
+        motif, the valid windows, four letter counts), stay within the slab budget (CRBM_SLAB_BYTES, or 256 MB)"""
+        budget = int(os.environ.get("CRBM_SLAB_BYTES", 256 << 20))
+        most = max(1, budget // (16 * self.num_motifs + 40))
+        for lo, hi in self._scan_cuts(stream, offsets):
+            r0 = int(np.searchsorted(offsets, lo, side="left"))
+            r1 = int(np.searchsorted(offsets, hi + 1, side="left"))
+            for r in range(r0, r1, most):
+                yield r, min(r + most, r1)
+
+    def recordSummary(self, stream, offsets):
+        """How well the model explains every record of a stream, and where: freeEnergy and motifBestSites for records of
+        any length with N.  `stream` and `offsets` are those of sequences.seqsToStream / fastaToStream (R records,
+        R + 1 offsets, one code 4 between two records); `offsets` is required -- a stream without records of its own is
+        offsets=[0, len(stream) + 1].  Returns a dict:
+          windows   (R,) int64     valid windows of the record: all motif_length codes are letters
+          letters   (R, 4) int64   its A, C, G, T
+          per_motif (R, K) float32 -sum over its valid windows and the strands of softplus(x_k), x as in variantEffects
+                                   (single-stranded models: the forward activation alone).  The hidden part only: the
+                                   visible bias is NOT added to every column, unlike freeEnergy(permotif=True) and the
+                                   reference's _freeEnergyPerMotif
+          fe        (R,) float32   sum_k per_motif[r, k] - sum_a letters[r, a] c[a]: variantEffects' F of the record
+                                   alone; L * freeEnergy(codes) for a record of L letters without N
+          start, strand, prob (R, K) int32, int8, float32: the best site of every (record, motif) with scanSites'
+                                   scores (the same bits), start relative to the record, ties to the smaller start,
+                                   then to + (motifBestSites' rule)
+          unit      float          the fixed-point unit of the free-energy sums: a window's softplus is rounded to it
+                                   once, then integers are added -- the same bits in every run, for every
+                                   CRBM_SLAB_BYTES, and the rows of two streams joined by a code 4 are the rows of one
+                                   followed by the rows of the other
+        A record without a valid window (shorter than motif_length, empty, all N) has windows 0, a per_motif row of
+        exact zeros, start -1, strand 0 and prob 0.  The models scanSites refuses are refused."""
+        if offsets is None:
+            raise ValueError("offsets is required (sequences.seqsToStream; one record: offsets=[0, len(stream) + 1])")
+        _, stream, offsets = self._scan_input(stream, 0.0, offsets)
+        R = offsets.size - 1
+        pieces = [self._records_call(stream[offsets[r0]:offsets[r1] - 1], np.ascontiguousarray(offsets[r0:r1 + 1] - offsets[r0]))
+                  for r0, r1 in self._records_cuts(stream, offsets)] if R else []
+        if not pieces:
+            pieces = [self._records_call(stream, np.zeros(1, np.int64))]
+        out = {k: np.concatenate([p[k] for p in pieces]) for k in ("windows", "letters", "per_motif", "fe", "start", "strand", "prob")}
+        out["strand"] = out["strand"].astype(np.int8)
+        out["unit"] = pieces[0]["unit"]
+        return out
+
     @staticmethod
     def _letter_codes(x, what, V):
         """`what` (alt or ref of variantEffects) as (V,) uint8 codes: a uint8 array of codes, or a string / an array of

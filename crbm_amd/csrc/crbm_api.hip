@@ -180,6 +180,10 @@ struct crbm_handle {
   DevBuf<float> ais_betas, ais_base, ais_logw;
   DevBuf<uint8_t> ais_state;
   DevBuf<unsigned long long> hist;                 // score histogram (crbm_scan_histogram_codes): [K][S][nbins], then the valid windows; both streams add into it
+  // record summaries (crbm_scan_records_codes): the call's accumulators -- sums [nrec][K], keys [nrec][K], counts [nrec][5] --
+  // and the device copy of rec_start; both streams add into the accumulators
+  DevBuf<unsigned long long> rec_acc;
+  DevBuf<long long> rec_start;
   float* d_sums = nullptr;
   int dataset_n[CRBM_DATASET_SLOTS] = {0, 0}, dataset_L[CRBM_DATASET_SLOTS] = {0, 0};
   int slot = 0;
@@ -1786,7 +1790,7 @@ int crbm_destroy(crbm_handle* h) {
     b.scan_valid.release(); b.scan_off.release(); b.scan_lanes.release(); b.scan_tiles.release();
     b.mut_df.release(); b.mut_pll.release(); b.mut_rows.release(); b.var_windows.release();
   }
-  h->ais_betas.release(); h->ais_base.release(); h->ais_logw.release(); h->ais_state.release(); h->hist.release();
+  h->ais_betas.release(); h->ais_base.release(); h->ais_logw.release(); h->ais_state.release(); h->hist.release(); h->rec_acc.release(); h->rec_start.release();
   if (h->jk.module) (void)hipModuleUnload(h->jk.module);
   if (h->jg.module) (void)hipModuleUnload(h->jg.module);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -2742,6 +2746,86 @@ int scan_hist_any(crbm_handle* h, const uint8_t* codes, int64_t T, float lo, flo
   return CRBM_OK;
 }
 
+// ---- record summaries (crbm_scan_records_codes) ---------------------------------------------------------------------
+// A StreamSweep with one launch per segment, like the histogram: crbm_scan_records adds the segment's windows and
+// letters into the call's accumulators (h->rec_acc: sums, keys, counts), zeroed on the main stream before the first
+// segment and copied back once after both streams are idle; records_finish (crbm_sweep.h) makes the outputs of them.
+// Everything that can be refused on the host is refused before anything is launched.  A stream shorter than a motif
+// has no window: its letters are counted on the host.  CRBM_RECORDS_TIMING=1: tools/bench_records.py.
+int scan_records_any(crbm_handle* h, const uint8_t* codes, int64_t T, const int64_t* rec_start, int64_t nrec, int64_t* windows,
+                     int64_t* letters, float* fe, float* fe_per_motif, int32_t* best_start, int32_t* best_strand, float* best_prob,
+                     double* unit) {
+  StreamSweep sw{h, "crbm_scan_records_codes"};
+  int rc = sw.admit(codes, T);
+  if (rc) return rc;
+  ARGCHK(rec_start, "null argument");
+  ARGCHK(nrec >= 0 && nrec <= (int64_t)INT32_MAX, "nrec must lie in [0, 2^31 - 1]");
+  ARGCHK(nrec > 0 || T == 0, "crbm_scan_records_codes: no records, but letters");
+  if (nrec > 0) {
+    const char* bad = records_check(codes, T, rec_start, nrec);
+    ARGCHK(!bad, std::string("crbm_scan_records_codes: ") + (bad ? bad : ""));
+  }
+  const int K = h->K, M = sw.M;
+  rc = sweep_begin(h);                   // (the parameters are at rest)
+  if (rc) return rc;
+  std::vector<float> W((size_t)K * 4 * M), b((size_t)K);
+  float c[4];
+  HIPCHK(hipMemcpyAsync(W.data(), h->dW, W.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(b.data(), h->db, b.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(c, h->dc, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const int e = records_unit_exp(records_x_max(W.data(), b.data(), K, M), sw.S);
+  if (unit) *unit = records_unit(e);
+  if (nrec == 0) return CRBM_OK;
+  const bool want_counts = windows || letters || fe, want_fe = fe || fe_per_motif, want_best = best_start || best_strand || best_prob;
+  ARGCHK(want_counts || want_fe || want_best, "null argument: at least one output is required");
+  const size_t cells = (size_t)nrec * K;
+  const size_t off_keys = want_fe ? cells : 0, off_counts = off_keys + (want_best ? cells : 0);
+  const size_t words = off_counts + (want_counts ? (size_t)nrec * 5 : 0);
+  std::vector<unsigned long long> acc(words, 0ull);
+  if (T < M) {                           // no window anywhere
+    for (int64_t i = 0; i < T; ++i) ARGCHK(codes[i] <= 4, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
+    if (want_counts)
+      for (int64_t r = 0; r < nrec; ++r)
+        for (int64_t i = rec_start[r]; i < rec_start[r + 1] - 1; ++i)
+          if (codes[i] < 4) ++acc[off_counts + 5 * (size_t)r + 1 + codes[i]];
+  } else {
+    rc = sw.begin(T);
+    if (rc) return rc;
+    static_assert(sizeof(long long) == sizeof(int64_t), "rec_start goes up as it is");
+    HIPCHK(h->rec_acc.ensure(words));
+    HIPCHK(h->rec_start.ensure((size_t)nrec + 1));
+    HIPCHK(hipMemsetAsync(h->rec_acc.p, 0, words * sizeof(unsigned long long), h->stream));
+    HIPCHK(hipMemcpyAsync(h->rec_start.p, rec_start, ((size_t)nrec + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));               // zeroed and in place before either stream adds
+    const int nslab = sw.nslab, starts_all = sw.plan.starts_all;
+    rc = sw.run(codes, "CRBM_RECORDS_TIMING",
+      [&](const SweepSet& set, int, const ScanInput& in, int start, int cnt) -> int {
+        ScanRecordsArgs a{in};
+        a.rec_start = h->rec_start.p;
+        a.sums = want_fe ? h->rec_acc.p : nullptr;
+        a.best = want_best ? h->rec_acc.p + off_keys : nullptr;
+        a.counts = want_counts ? h->rec_acc.p + off_counts : nullptr;
+        a.pos0 = start; a.nrec = (int32_t)nrec;
+        a.own = start + cnt == starts_all ? cnt + M - 1 : cnt;   // the last segment counts the letters behind its starts
+        a.scale = ldexpf(1.f, e); a.pad_ = 0;
+        // four waves a block, two blocks a CU: a wave's run is long (32 tiles of a 4M-start segment on 256 CUs), because a
+        // run ends in a flush, and the flushes of one long record all meet on the same K addresses
+        const int tiles = (a.own + 63) / 64;
+        const unsigned gx = (unsigned)std::max(1, std::min((tiles + 31) / 32, std::max(1, h->num_cu * 2 / nslab)));
+        HIPCHK(jit_launch(sw.kjk->scan_records, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(*sw.kms), set.st));
+        return CRBM_OK;
+      },
+      [](const SweepSet&, int, const ScanInput&, int, int) -> int { return CRBM_OK; });
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(acc.data(), h->rec_acc.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  records_finish(nrec, K, h->ds, e, c, want_fe ? acc.data() : nullptr, want_best ? acc.data() + off_keys : nullptr,
+                 want_counts ? acc.data() + off_counts : nullptr, windows, letters, fe, fe_per_motif, best_start, best_strand, best_prob);
+  return CRBM_OK;
+}
+
 // ---- variant effects (crbm_variant_effects_codes) -------------------------------------------------------------------
 // A two-stream sweep over the variant list in chunks (crbm_sweep.h, variant_plan).  Everything that can be refused is
 // refused on the host before anything is launched: outputs are then left as they were.  Per chunk, on its set's
@@ -3255,6 +3339,13 @@ int crbm_scan_histogram_codes(crbm_handle* h, const uint8_t* codes, int64_t T, f
                               uint64_t* counts, int64_t* windows) {
   ENTER();
   return scan_hist_any(h, codes, T, lo, hi, nbins, counts, windows);
+}
+
+int crbm_scan_records_codes(crbm_handle* h, const uint8_t* codes, int64_t T, const int64_t* rec_start, int64_t nrec,
+                            int64_t* windows, int64_t* letters, float* fe, float* fe_per_motif, int32_t* best_start,
+                            int32_t* best_strand, float* best_prob, double* unit) {
+  ENTER();
+  return scan_records_any(h, codes, T, rec_start, nrec, windows, letters, fe, fe_per_motif, best_start, best_strand, best_prob, unit);
 }
 
 int crbm_variant_effects_codes(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t nvar, const int64_t* pos,

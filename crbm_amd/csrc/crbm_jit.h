@@ -31,7 +31,7 @@ struct JitKernels {
   hipFunction_t build_tables = nullptr, update_tables = nullptr, update_tables_ipc = nullptr, hgv = nullptr, gibbs = nullptr /* dense top-down; null if the model has none */,
                 build_gather_solo = nullptr /* gather table of the solo letter grouping */, slab_hgv = nullptr, slab_tables = nullptr, slab_stats_data = nullptr, slab_stats_model = nullptr, slab_fe = nullptr /* the model as a slab of a larger one: empty beyond 64 motifs */,
                 gibbs_sparse = nullptr, gibbs_sparse_stats = nullptr /* empty unless Cfg::FUSE_STATS */, train_local = nullptr /* ditto */, stats_mfma_data = nullptr, stats_mfma_model = nullptr,
-                free_energy = nullptr, hit_summary = nullptr, motif_sites = nullptr, mutagenesis = nullptr /* empty for pooled models */, ais = nullptr /* ditto */, scan_sites = nullptr /* ditto */, scan_hist = nullptr /* ditto */, variant_effects = nullptr /* ditto */, allele_effects = nullptr /* ditto */;
+                free_energy = nullptr, hit_summary = nullptr, motif_sites = nullptr, mutagenesis = nullptr /* empty for pooled models */, ais = nullptr /* ditto */, scan_sites = nullptr /* ditto */, scan_hist = nullptr /* ditto */, scan_records = nullptr /* ditto */, variant_effects = nullptr /* ditto */, allele_effects = nullptr /* ditto */;
   bool from_cache = false;
   std::string cache_file;
 };
@@ -115,6 +115,7 @@ inline std::string jit_stub(int K, int M, int DS, int G, int GS, int POOL, int g
            "extern \"C\" __global__ void __launch_bounds__(256) crbm_ais(crbm::AisArgs a) { crbm::ais_body<ModelCfg>(a); }\n"
            "extern \"C\" __global__ void __launch_bounds__(256) crbm_scan_sites(crbm::ScanArgs a) { crbm::scan_sites_body<ModelCfg>(a); }\n"
            "extern \"C\" __global__ void __launch_bounds__(512) crbm_scan_hist(crbm::ScanHistArgs a) { crbm::scan_hist_body<ModelCfg>(a); }\n"
+           "extern \"C\" __global__ void __launch_bounds__(256) crbm_scan_records(crbm::ScanRecordsArgs a) { crbm::scan_records_body<ModelCfg>(a); }\n"
            "extern \"C\" __global__ void __launch_bounds__(256) crbm_variant_effects(crbm::VariantArgs a) { crbm::variant_effects_body<ModelCfg>(a); }\n"
            "extern \"C\" __global__ void __launch_bounds__(256) crbm_allele_effects(crbm::AlleleArgs a) { crbm::allele_effects_body<ModelCfg>(a); }\n",
            slab ? 1 : 0, attr, sattr, K, M, DS, G, POOL, K, M, DS, GS, POOL, gibbs_tb, gibbs_tb);
@@ -262,7 +263,7 @@ inline int jit_load(int K, int M, int DS, int G, int GS, int POOL, int gibbs_wpe
       {"crbm_stats_mfma_model", &out->stats_mfma_model}, {"crbm_free_energy", &out->free_energy},
       {"crbm_hit_summary", &out->hit_summary}, {"crbm_motif_sites", &out->motif_sites},
       {"crbm_mutagenesis", &out->mutagenesis}, {"crbm_ais", &out->ais}, {"crbm_scan_sites", &out->scan_sites},
-      {"crbm_scan_hist", &out->scan_hist}, {"crbm_variant_effects", &out->variant_effects},
+      {"crbm_scan_hist", &out->scan_hist}, {"crbm_scan_records", &out->scan_records}, {"crbm_variant_effects", &out->variant_effects},
       {"crbm_allele_effects", &out->allele_effects}};
   for (auto& s : syms) {
     e = hipModuleGetFunction(s.f, out->module, s.name);

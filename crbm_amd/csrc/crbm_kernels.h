@@ -3567,6 +3567,207 @@ __device__ void allele_effects_body(const AlleleArgs& a) {
   }
 }
 
+// ===========================================================================
+// Record summaries (crbm_scan_records_codes): per record of a stream -- records are separated by one code 4, rec_start
+// holds their first positions and T + 1 behind them (sequences.seqsToStream) -- the valid windows, the letter counts,
+// per motif the free-energy sum over the record's valid windows and the best site.  A window, and a letter, belongs to
+// the record its position lies in; a separator belongs to the record in front of it and contributes nothing.
+//   free energy  z as free_energy_body gathers it (conv_gather_quads per strand, strand <= DS; for a double-stranded
+//                model that is window_strand_z's z, gathered once).  ONE WINDOW IS THE UNIT OF ROUNDING: the lane adds
+//                the window's softplus over the strands in float32, + before -, rounds to nearest into fixed point
+//                (`scale` units per 1.0, a power of two: crbm_layout.h, records_unit_exp) and from there on everything
+//                is a 64-bit integer add.  No float is combined across windows: which windows share a tile, a wave or a
+//                segment changes with the segmenting, the sum of integers does not.
+//   best site    motif_sites_body's key (site_key) with the start relative to the record, reduced with max.
+//   letters      position s of a segment counts when s < own: a segment owns the positions of its window starts, the
+//                last one the M - 1 letters behind them too -- every letter of the stream exactly once.
+// A wave owns a CONTIGUOUS run of tiles of 64 positions, a lane one position per tile.  Every lane keeps integer sums,
+// keys and counts of the record the wave is in (`cur`) in registers, for NQW motif quads at a time (the outer loop);
+// when the record changes, and at the end of the run, the wave flushes: one integer wave sum, one key maximum and one
+// atomic per motif on the call's accumulators, then zeros.  A record of 10^8 letters costs a wave one flush per run, not
+// one per tile.  A tile inside one record is the wave-uniform path (no search); a tile with a record boundary finds
+// every lane's record by a binary search over at most 64 entries of rec_start (a record holds at least its separator)
+// and folds its records in ascending order, flushing between them.  Integer add and max commute: the same bits for
+// every geometry, segmenting and run.  blockIdx.y is the slab of a generic DNA model, which owns its columns
+// [k0 + kskip, k0 + kend); slab 0 counts windows and letters, on its first group of quads.
+// ===========================================================================
+struct ScanRecordsArgs : ScanInput {
+  const long long* rec_start;            // [nrec + 1] stream positions
+  unsigned long long* sums;              // [nrec][K] fixed-point softplus sums, or null
+  unsigned long long* best;              // [nrec][K] keys, or null
+  unsigned long long* counts;            // [nrec][5]: valid windows, then A, C, G, T; or null
+  long long pos0;                        // stream position of the segment's first letter
+  int32_t nrec;
+  int32_t own;                           // positions of the segment whose letters it counts
+  float scale;                           // fixed-point units per 1.0
+  int32_t pad_;
+};
+
+// sum over the wave of 64-bit integers (all lanes call it; every lane gets it): wave_sum's DPP moves on both halves
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+  auto step = [&](auto CTRL, auto ROW_MASK) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, decltype(CTRL)::value, decltype(ROW_MASK)::value, 0xf, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), decltype(CTRL)::value, decltype(ROW_MASK)::value, 0xf, false);
+    v += ((unsigned long long)hi << 32) | lo;
+  };
+  step(IC<0x121>{}, IC<0xf>{});
+  step(IC<0x122>{}, IC<0xf>{});
+  step(IC<0x124>{}, IC<0xf>{});
+  step(IC<0x128>{}, IC<0xf>{});
+  step(IC<0x142>{}, IC<0xa>{});
+  step(IC<0x143>{}, IC<0xc>{});
+  return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) |
+         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
+}
+// a window's softplus sum in fixed point: v * scale rounded to nearest (ties to even); v >= 0, v * scale < 2^31
+__device__ __forceinline__ uint32_t records_fx(float v, float scale) { return (uint32_t)__builtin_rintf(v * scale); }
+// the record of stream position p: the largest r in [lo, hi] with rec_start[r] <= p (rec_start[lo] <= p)
+__device__ __forceinline__ int record_of(const long long* rec_start, int lo, int hi, long long p) {
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (rec_start[mid] <= p) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+template <class C>
+__device__ void scan_records_body(const ScanRecordsArgs& a) {
+  if constexpr (C::POOL == 1) {       // refused on the host, as the scan
+    constexpr int M = C::M, S = C::DS ? 2 : 1;
+    constexpr int NQW = C::NQ < 4 ? C::NQ : 4, NV = 4 * NQW;
+    HIP_DYNAMIC_SHARED(float, smem);
+    float* Tf = smem;
+    const ScanInput& in = a;
+    const int y = (int)blockIdx.y;
+    const SlabSpan span = slab_span<C>(in.plan, y);
+    copy_tables<C::TAB>(Tf, in.tables + (size_t)y * in.table_stride + C::OFF_TF);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const bool want_fe = a.sums != nullptr, want_best = a.best != nullptr;
+    const int K = in.plan.K;
+    // the wave's run of tiles
+    const int ntiles = (a.own + 63) >> 6;
+    const int nw_all = (int)gridDim.x * nwaves, per = (ntiles + nw_all - 1) / nw_all;
+    const int t0 = min(ntiles, ((int)blockIdx.x * nwaves + wave) * per), t1 = min(ntiles, t0 + per);
+    if (t0 >= t1) return;
+    const int r_run = record_of(a.rec_start, 0, a.nrec - 1, a.pos0 + 64ll * t0);
+#pragma unroll 1
+    for (int q0 = 0; q0 < C::NQ; q0 += NQW) {
+      const bool counting = q0 == 0 && y == 0 && a.counts != nullptr;
+      if (!counting && !want_fe && !want_best) continue;
+      unsigned long long acc[NV], key[NV];
+      uint32_t nwin = 0, nlet[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < NV; ++j) { acc[j] = 0ull; key[j] = 0ull; }
+      int cur = -1;                    // the record the registers belong to
+      auto flush = [&]() {
+        if (cur < 0) return;           // wave-uniform
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+          const int kk = 4 * q0 + j;
+          if (kk < span.kskip || kk >= span.kend) continue;    // wave-uniform
+          const size_t cell = (size_t)cur * K + span.k0 + kk;
+          if (want_fe) {
+            const unsigned long long s = wave_sum_u64(acc[j]);
+            if (lane == 0 && s) atomicAdd(a.sums + cell, s);
+          }
+          if (want_best) {
+            const unsigned long long k = wave_max_key(key[j]);
+            if (lane == 0 && k) atomicMax(a.best + cell, k);
+          }
+          acc[j] = 0ull; key[j] = 0ull;
+        }
+        if (counting) {
+          const unsigned long long w = wave_sum_u64(nwin);
+          if (lane == 0 && w) atomicAdd(a.counts + (size_t)cur * 5, w);
+#pragma unroll
+          for (int l = 0; l < 4; ++l) {
+            const unsigned long long c = wave_sum_u64(nlet[l]);
+            if (lane == 0 && c) atomicAdd(a.counts + (size_t)cur * 5 + 1 + l, c);
+            nlet[l] = 0u;
+          }
+          nwin = 0u;
+        }
+      };
+      int r0 = r_run;
+#pragma unroll 1
+      for (int t = t0; t < t1; ++t) {
+        const int s = 64 * t + lane;
+        const long long p0 = a.pos0 + 64ll * t, p = p0 + lane;
+        const bool single = p0 + 63 < a.rec_start[r0 + 1];             // wave-uniform: the tile lies in one record
+        const int r_lane = single ? r0 : record_of(a.rec_start, r0, min(r0 + lane, a.nrec - 1), p);
+        const bool ok = s < in.starts && window_valid<M>(in.valid, s);
+        const bool letter = s < a.own && ((in.valid[s >> 6] >> (s & 63)) & 1ull);
+        uint32_t fx[NV], pb[NV], minus = 0u;    // the window's fixed-point sums, the bits of its best scores, whose is the - strand's
+#pragma unroll
+        for (int j = 0; j < NV; ++j) { fx[j] = 0u; pb[j] = 0u; }
+        if (ok && (want_fe || want_best)) {
+          const LetterWin<M> w = letter_window<M>(in.letters, s);
+          float sp[NV];
+#pragma unroll
+          for (int j = 0; j < NV; ++j) sp[j] = 0.f;
+#pragma unroll
+          for (int strand = 0; strand < S; ++strand) {
+            float z[NV];
+            window_strand_z<C, NQW>(Tf, w, q0, strand, z);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+              if (want_best) {
+                const uint32_t b = __float_as_uint(sigmoid_z(z[j]));
+                if (strand == 0 || b > pb[j]) {                        // a tie stays with +
+                  pb[j] = b;
+                  minus = strand ? minus | (1u << j) : minus;
+                }
+              }
+              if (C::DS && want_fe) sp[j] += softplus_of_z(z[j]);
+            }
+          }
+          if (!C::DS && want_fe) {     // a single-stranded model's free energy sees the forward activation alone
+            float z[NV];
+            conv_gather_quads<C, NQW>(Tf, w, q0, z);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) sp[j] = softplus_of_z(z[j]);
+          }
+          if (want_fe) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) fx[j] = records_fx(sp[j], a.scale);
+          }
+        }
+        const uint32_t code = (in.letters[s >> 4] >> (2 * (s & 15))) & 3u;   // (inside the letter words for every s of a tile)
+        // the records of the tile that have something to add, in ascending order
+        unsigned long long todo = __ballot(ok || letter);
+        while (todo) {                 // wave-uniform
+          const int r = __builtin_amdgcn_readlane(r_lane, __ffsll(todo) - 1);
+          const bool mine = r_lane == r;
+          if (r != cur) { flush(); cur = r; }
+          if (mine && ok) {
+            const int rel = (int)(p - a.rec_start[r]);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+              acc[j] += fx[j];
+              if (want_best) {
+                const unsigned long long k = ((unsigned long long)pb[j] << 32) |
+                                             (unsigned long long)(0xFFFFFFFFu - (uint32_t)(2 * rel + (int)((minus >> j) & 1u)));
+                key[j] = k > key[j] ? k : key[j];
+              }
+            }
+            nwin += 1u;
+          }
+          if (mine && letter) {
+#pragma unroll
+            for (int l = 0; l < 4; ++l) nlet[l] += code == (uint32_t)l ? 1u : 0u;
+          }
+          todo &= ~__ballot(mine);
+        }
+        // the record of the next tile's first position: at most one further than that of this tile's last
+        const int r63 = __builtin_amdgcn_readlane(r_lane, 63);
+        r0 = (r63 + 1 < a.nrec && a.rec_start[r63 + 1] <= p0 + 64) ? r63 + 1 : r63;
+      }
+      flush();
+    }
+  }
+}
+
 #ifdef CRBM_DEFINE_MISC_KERNELS
 // ===========================================================================
 // Model-independent kernels, compiled ahead of time into libcrbm_hip.so.

@@ -92,6 +92,25 @@ inline HistPlan hist_plan(int tab_bytes, int NQ, int S, int nbins, int want_copi
   p.lds = tab_bytes + quad * p.gq * p.copies + 4;
   return p;
 }
+// Record summaries (crbm_kernels.h, scan_records_body): the free-energy sums of a call are 64-bit integers in units of
+// 2^-e.  A window adds softplus over S strands, each at most max(x_max, 0) + log 2 with
+// x_max = max_k (b_k + sum_j max_a W[k,a,j]), and one call sees fewer than 2^31 windows: e is the finest exponent,
+// at most 32, with 2^31 S (max(x_max, 0) + log 2) 2^e < 2^62.  A window's term then stays below 2^31 units (the kernel
+// keeps it in 32 bits) and a sum below 2^62, a factor of four under what the accumulator holds (room for the float32
+// rounding of x).  The unit depends on the model alone, never on the stream.
+inline int records_unit_exp(double x_max, int S) {
+  const double per_window = (double)S * ((x_max > 0.0 ? x_max : 0.0) + 0.6931471805599453);
+  const double limit = 4611686018427387904.0;        // 2^62
+  double scaled = per_window * 2147483648.0 * 4294967296.0;   // 2^31 windows, e = 32
+  int e = 32;
+  while (scaled >= limit && e > -96) { scaled *= 0.5; --e; }
+  return e;
+}
+inline double records_unit(int e) {                  // 2^-e
+  double u = 1.0;
+  for (int i = 0; i < (e < 0 ? -e : e); ++i) u *= e < 0 ? 2.0 : 0.5;
+  return u;
+}
 // Largest motif length the letter windows hold (two 64-bit words); the number of motifs is
 // bounded by what the LDS holds (tables + one chain: choose_gibbs_geometry refuses beyond)
 // and by the statistics kernel (one role of 64 threads per 16 motifs, at most 1024 threads per block).

@@ -11,6 +11,7 @@
 // succeeds never calls drain().  Below it: stream_plan, the segments a stream sweep hands to run_slabs.
 #pragma once
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
@@ -165,6 +166,67 @@ inline long gather_haplotypes(const uint8_t* codes, int64_t T, const int64_t* po
     table[i] = e;
   }
   return at;
+}
+
+// Record summaries (crbm_api.hip, scan_records_any), the host's part.  records_check: what is wrong with the record
+// starts of a stream of T codes (sequences.seqsToStream: nrec + 1 entries from 0 on, every record followed by one
+// code 4, T + 1 last), or null.  nrec >= 1.
+inline const char* records_check(const uint8_t* codes, int64_t T, const int64_t* rec_start, int64_t nrec) {
+  if (rec_start[0] != 0) return "rec_start must start at 0";
+  for (int64_t r = 0; r < nrec; ++r)
+    if (rec_start[r + 1] <= rec_start[r]) return "rec_start must ascend (every record is followed by one separator)";
+  if (rec_start[nrec] != T + 1) return "the last entry of rec_start must be T + 1";
+  for (int64_t r = 1; r < nrec; ++r)
+    if (codes[rec_start[r] - 1] != 4) return "records must be separated by a code 4";
+  return nullptr;
+}
+// x_max of records_unit_exp from the model's parameters W [K][4][M], b [K]
+inline double records_x_max(const float* W, const float* b, int K, int M) {
+  double best = 0.0;
+  for (int k = 0; k < K; ++k) {
+    double x = b[k];
+    for (int j = 0; j < M; ++j) {
+      float m = W[((size_t)k * 4) * M + j];
+      for (int a = 1; a < 4; ++a) m = std::max(m, W[((size_t)k * 4 + a) * M + j]);
+      x += m;
+    }
+    best = k == 0 ? x : std::max(best, x);
+  }
+  return best;
+}
+// records_finish: the outputs of crbm_scan_records_codes from the call's accumulators -- sums [nrec][K] in units of
+// 2^-e, keys [nrec][K] (crbm_kernels.h, site_key; 0: no valid window), counts [nrec][5] (valid windows, A, C, G, T).  A
+// sum becomes a float32 with one rounding; fe is formed in double, ascending k, then ascending letter, and rounded
+// once.  Any output, and with it its accumulator, may be null.
+inline void records_finish(int64_t nrec, int K, int ds, int e, const float* c, const unsigned long long* sums,
+                           const unsigned long long* keys, const unsigned long long* counts, int64_t* windows, int64_t* letters,
+                           float* fe, float* fe_per_motif, int32_t* best_start, int32_t* best_strand, float* best_prob) {
+  const double unit = records_unit(e);
+  for (int64_t r = 0; r < nrec; ++r) {
+    if (windows) windows[r] = (int64_t)counts[5 * r];
+    if (letters)
+      for (int a = 0; a < 4; ++a) letters[4 * r + a] = (int64_t)counts[5 * r + 1 + a];
+    if (fe_per_motif)
+      for (int k = 0; k < K; ++k) {
+        const unsigned long long s = sums[r * K + k];
+        fe_per_motif[r * K + k] = s ? -ldexpf((float)s, -e) : 0.f;
+      }
+    if (fe) {
+      double acc = 0.0;
+      for (int k = 0; k < K; ++k) acc -= (double)sums[r * K + k] * unit;
+      for (int a = 0; a < 4; ++a) acc -= (double)counts[5 * r + 1 + a] * (double)c[a];
+      fe[r] = (float)acc;
+    }
+    for (int k = 0; k < K && keys; ++k) {
+      const unsigned long long key = keys[r * K + k];
+      const uint32_t low = 0xFFFFFFFFu - (uint32_t)key, bits = (uint32_t)(key >> 32);
+      float p;
+      memcpy(&p, &bits, 4);
+      if (best_start) best_start[r * K + k] = key ? (int32_t)(low >> 1) : -1;
+      if (best_strand) best_strand[r * K + k] = key && ds ? ((low & 1u) ? -1 : 1) : 0;
+      if (best_prob) best_prob[r * K + k] = key ? p : 0.f;
+    }
+  }
 }
 
 }  // namespace crbm

@@ -262,6 +262,41 @@ int crbm_scan_sites_codes(crbm_handle* h, const uint8_t* codes, int64_t T, float
 int crbm_scan_histogram_codes(crbm_handle* h, const uint8_t* codes, int64_t T, float lo, float hi, int32_t nbins,
                               uint64_t* counts, int64_t* windows);
 
+/* ---- record summaries: free energy and best site of every record of a stream --------
+ * The per-sequence numbers of crbm_free_energy and crbm_motif_sites' best site for records of any length with gaps.
+ * Stream, codes and window validity as crbm_scan_sites_codes.  rec_start holds nrec + 1 entries in the convention of
+ * sequences.seqsToStream: record r is codes [rec_start[r], rec_start[r+1] - 1), one code 4 follows every record but the
+ * last, rec_start[0] = 0 and rec_start[nrec] = T + 1.  A window belongs to the record its start lies in; the separator
+ * keeps windows from spanning two records.  Per record r:
+ *   windows[r]        = its valid windows                                                          (nrec) int64
+ *   letters[r][a]     = its letters a = A,C,G,T                                                    (nrec,4) int64
+ *   fe_per_motif[r,k] = - sum over its valid windows and the strands of softplus(x_k), x as crbm_variant_effects_codes
+ *                       documents F (each strand of a double-stranded model, the forward activation alone of a
+ *                       single-stranded one).  The hidden part only: the visible bias is NOT added to every column,
+ *                       unlike crbm_free_energy_per_motif                                          (nrec,K) fp32
+ *   fe[r]             = sum_k fe_per_motif[r,k] - sum_a letters[r][a] c[a]: the stream free energy F restricted to
+ *                       the record; L * crbm_free_energy for a record of L letters without a gap   (nrec) fp32
+ *   best_start, best_strand, best_prob [r,k]: the best site of (record, motif) with the scores of
+ *                       crbm_scan_sites_codes (the same bits), start relative to the record, ties to the smaller start,
+ *                       then to + (crbm_motif_sites' rule)                                          (nrec,K) int32, int32, fp32
+ * A record without a valid window (shorter than M, empty, all N) has windows 0, a fe_per_motif row of exact zeros,
+ * best_start -1, best_strand 0 and best_prob 0.
+ * The free-energy sums are 64-bit fixed point: a window's softplus, summed over the strands in fp32 (+ before -), is
+ * rounded to nearest into units of *unit once, and only integers are added from there; *unit = 2^-e is the finest
+ * power of two, e <= 32, with 2^31 S (max(x_max, 0) + log 2) 2^e < 2^62, x_max = max_k (b_k + sum_j max_a W[k,a,j]):
+ * it depends on the model alone and no stream a call accepts can overflow a sum.  A sum becomes fp32 with one rounding;
+ * fe is formed in double (ascending k, then ascending letter) and rounded once.  Hence the same bits in every run, for
+ * every launch geometry and every CRBM_SLAB_BYTES, and the rows of A ++ [4] ++ B are the rows of A followed by the
+ * rows of B.  Any output may be NULL (at least one of those above is required when nrec > 0); unit may be NULL.
+ * nrec == 0 requires T == 0 and writes nothing but *unit.
+ * Served: exactly the models crbm_scan_sites_codes serves.
+ * CRBM_ERR_INVALID: what the scan refuses (pooling > 1, another alphabet, a generic-only model, a code above 4, T < 0,
+ * T > 2^31 - 1); a rec_start that does not start at 0, does not ascend, does not end with T + 1, or whose joints are
+ * not codes 4 -- found on the host before anything is launched.  The handle stays usable after a refusal. */
+int crbm_scan_records_codes(crbm_handle* h, const uint8_t* codes, int64_t T, const int64_t* rec_start, int64_t nrec,
+                            int64_t* windows, int64_t* letters, float* fe, float* fe_per_motif, int32_t* best_start,
+                            int32_t* best_strand, float* best_prob, double* unit);
+
 /* ---- variant effects: what a substitution changes in the free energy of a stream ---
  * Given a stream and a list of variants (position, alternative letter): how much does each variant change the model's
  * free energy, and which motif gains or loses the site.  Stream, codes and window validity as crbm_scan_sites_codes:
