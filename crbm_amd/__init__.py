@@ -10,6 +10,8 @@ from .sequences import (seqsToCodes, codesToOneHot, seqToOneHot, readSeqsFromFas
                         splitTrainingTest, fastaToCodes, writeFasta, load_sample, seqsToStream, fastaToStream, shuffleStream,
                         readVcf)
 from .calibrate import ScoreHistogram  # noqa: F401
-from .utils import saveMotifs, saveSites  # noqa: F401
+from .utils import saveMotifs, saveSites, runTSNE  # noqa: F401
+from .tsne import tsneEmbed, symmetrize  # noqa: F401
+from . import tsne  # noqa: F401
 
 __version__ = "0.1.0"

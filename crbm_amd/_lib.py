@@ -144,6 +144,11 @@ SIGNATURES = {
     "crbm_last_shader_clock": (_I32, [_H, _F]),
     "crbm_geometry_launches": (_I32, [_H, _I64P, _I64P]),
     "crbm_gibbs_state_bytes": (ctypes.c_int64, [_H]),
+    "crbm_tsne_neighbors": (_I32, [_H, _F, _I64, _I32, _I32, _I32P, _F]),
+    "crbm_tsne_affinities": (_I32, [_H, _F, _I64, _I32, ctypes.c_float, _F, _F]),
+    "crbm_tsne_descend": (_I32, [_H, _I64, _I64P, _I32P, _F, _F, _F, _F, _I32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                 _F, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "crbm_tsne_descend_ms": (_I32, [_H, _F]),
 }
 
 _lib = None

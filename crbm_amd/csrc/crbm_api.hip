@@ -6,6 +6,7 @@
 #include "crbm_jit.h"
 #include "crbm_plan.h"
 #include "crbm_sweep.h"
+#include "crbm_tsne.h"
 #include "../../include/crbm_amd.h"
 
 #include <dlfcn.h>
@@ -243,6 +244,7 @@ struct crbm_handle {
   int slab_n = 0;
   bool slab_hgv = false;               // the chain's h|v takes the slabs too (slab a multiple of ten motifs, or one slab: sampler groups)
   uint64_t slab_tables_version = 0;
+  float tsne_ms = 0.f;                 // device time of the iterations of the last crbm_tsne_descend call (HIP events)
   std::string slab_note;               // why the slabs are off, if they are (crbm_launch_info prints nothing of it; a debugging aid)
   std::string err;
 };
@@ -3741,6 +3743,166 @@ int64_t crbm_gibbs_state_bytes(const crbm_handle* h) {
   const int64_t masks = (int64_t)h->B * h->Lf * h->NW * 4 * (1 + h->ds);
   const int64_t vout = (int64_t)h->B * h->LWs * 4;
   return 2 * masks + vout;   // masks read + written, last visible sample written
+}
+
+}  // extern "C"
+
+// ---- t-SNE (crbm_tsne.h): the handle lends its device, stream and error string; the model plays no part --------------
+namespace {
+
+// device buffers of one call, freed whichever way the call ends
+struct TsneScratch {
+  std::vector<void*> ptrs;
+  ~TsneScratch() { for (void* p : ptrs) (void)hipFree(p); }
+  template <typename T>
+  hipError_t get(T** out, size_t count) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess) ptrs.push_back(p);
+    *out = static_cast<T*>(p);
+    return e;
+  }
+};
+
+unsigned tsne_grid(int64_t blocks) { return (unsigned)std::min<int64_t>(std::max<int64_t>(blocks, 1), 65535); }
+
+}  // namespace
+
+extern "C" {
+
+int crbm_tsne_neighbors(crbm_handle* h, const float* X, int64_t n, int32_t D, int32_t k, int32_t* idx, float* d2) {
+  ENTER();
+  ARGCHK(X && idx && d2, "null argument");
+  if (const char* why = tsne::neighbors_refusal(n, D, k)) return fail(h, CRBM_ERR_INVALID, why);
+  for (int64_t e = 0; e < n * D; ++e) ARGCHK(std::isfinite(X[e]), "X is not finite");
+  int waves = 8;                                     // queries per block; fewer where the lists and rows do not fit
+  while (waves > 1 && tsne::knn_lds_bytes(D, k, waves) > 128 * 1024) waves >>= 1;
+  const size_t lds = tsne::knn_lds_bytes(D, k, waves);
+  ARGCHK(lds <= 160 * 1024, "k and D leave no room in the LDS");
+  TsneScratch s;
+  float *dX = nullptr, *dd2 = nullptr;
+  int32_t* didx = nullptr;
+  HIPCHK(s.get(&dX, (size_t)n * D));
+  HIPCHK(s.get(&didx, (size_t)n * k));
+  HIPCHK(s.get(&dd2, (size_t)n * k));
+  HIPCHK(hipMemcpyAsync(dX, X, (size_t)n * D * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tsne::tsne_knn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const tsne::KnnArgs a{dX, didx, dd2, (int)n, D, k};
+  hipLaunchKernelGGL(tsne::tsne_knn_kernel, dim3(tsne_grid((n + waves - 1) / waves)), dim3(64 * waves), lds, h->stream, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(idx, didx, (size_t)n * k * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(d2, dd2, (size_t)n * k * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return CRBM_OK;
+}
+
+int crbm_tsne_affinities(crbm_handle* h, const float* d2, int64_t n, int32_t k, float perplexity, float* p, float* beta) {
+  ENTER();
+  ARGCHK(d2 && p && beta, "null argument");
+  if (const char* why = tsne::affinities_refusal(n, k, perplexity)) return fail(h, CRBM_ERR_INVALID, why);
+  for (int64_t e = 0; e < n * k; ++e) ARGCHK(std::isfinite(d2[e]) && d2[e] >= 0.f, "a distance is negative or not finite");
+  TsneScratch s;
+  float *dd2 = nullptr, *dp = nullptr, *dbeta = nullptr;
+  HIPCHK(s.get(&dd2, (size_t)n * k));
+  HIPCHK(s.get(&dp, (size_t)n * k));
+  HIPCHK(s.get(&dbeta, (size_t)n));
+  HIPCHK(hipMemcpyAsync(dd2, d2, (size_t)n * k * 4, hipMemcpyHostToDevice, h->stream));
+  const tsne::AffinityArgs a{dd2, dp, dbeta, (int)n, k, std::log((double)perplexity)};
+  hipLaunchKernelGGL(tsne::tsne_affinity_kernel, dim3(tsne_grid((n + 63) / 64)), dim3(64), 0, h->stream, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(p, dp, (size_t)n * k * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(beta, dbeta, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return CRBM_OK;
+}
+
+int crbm_tsne_descend(crbm_handle* h, int64_t n, const int64_t* indptr, const int32_t* indices, const float* values, float* y,
+                      float* velocity, float* gains, int32_t iterations, float exaggeration, float learning_rate, float momentum,
+                      float* grad_last, double* kl, double* z) {
+  ENTER();
+  ARGCHK(indptr && y && velocity && gains, "null argument");
+  ARGCHK(n >= 2 && n <= tsne::MAX_N, "t-SNE needs at least two rows (and at most 2^30)");
+  ARGCHK(indptr[0] == 0 && indptr[n] >= 0, "indptr must start at 0 and ascend");
+  ARGCHK(indptr[n] == 0 || (indices && values), "null argument");
+  if (const char* why = tsne::descend_refusal(n, indptr, indices, iterations)) return fail(h, CRBM_ERR_INVALID, why);
+  const size_t nnz = (size_t)indptr[n];
+  const int S = tsne::slices(n);
+  const int64_t chunks = tsne::sum_chunks(n);
+  TsneScratch s;
+  int64_t* dptr = nullptr;
+  int32_t* dind = nullptr;
+  float* dval = nullptr;
+  float2 *dy[2] = {nullptr, nullptr}, *dvel = nullptr, *dgain = nullptr, *dgrad = nullptr;
+  float4 *dpart = nullptr, *drs = nullptr;
+  double *dchunk = nullptr, *dklrow = nullptr, *dscalar = nullptr;   // dscalar: Z, KL
+  HIPCHK(s.get(&dptr, (size_t)n + 1));
+  HIPCHK(s.get(&dind, nnz));
+  HIPCHK(s.get(&dval, nnz));
+  HIPCHK(s.get(&dy[0], (size_t)n));
+  HIPCHK(s.get(&dy[1], (size_t)n));
+  HIPCHK(s.get(&dvel, (size_t)n));
+  HIPCHK(s.get(&dgain, (size_t)n));
+  HIPCHK(s.get(&dgrad, (size_t)n));
+  HIPCHK(s.get(&dpart, (size_t)n * S));
+  HIPCHK(s.get(&drs, (size_t)n));
+  HIPCHK(s.get(&dchunk, (size_t)chunks));
+  HIPCHK(s.get(&dklrow, (size_t)n));
+  HIPCHK(s.get(&dscalar, 2));
+  HIPCHK(hipMemcpyAsync(dptr, indptr, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  if (nnz) {
+    HIPCHK(hipMemcpyAsync(dind, indices, nnz * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dval, values, nnz * 4, hipMemcpyHostToDevice, h->stream));
+  }
+  HIPCHK(hipMemcpyAsync(dy[0], y, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dvel, velocity, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dgain, gains, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(dscalar, 0, 16, h->stream));
+  // iterations == 0: one evaluation at y (gradient, KL, Z), nothing moves
+  const int passes = iterations > 0 ? iterations : 1;
+  const unsigned row_grid = tsne_grid((n + 255) / 256), chunk_grid = tsne_grid(chunks);
+  int cur = 0;
+  HIPCHK(hipEventRecord(h->ev0, h->stream));
+  for (int it = 0; it < passes; ++it) {
+    const bool last = it == passes - 1;
+    const tsne::RepulsionArgs ra{dy[cur], dpart, (int)n, S, tsne::slice_tiles(n)};
+    hipLaunchKernelGGL(tsne::tsne_repulsion_kernel, dim3(row_grid, S), dim3(256), tsne::TJ * 8, h->stream, ra);
+    const tsne::CombineArgs ca{dpart, drs, dchunk, (int)n, S};
+    hipLaunchKernelGGL(tsne::tsne_combine_kernel, dim3(chunk_grid), dim3(256), tsne::SUM_CHUNK * 8, h->stream, ca);
+    const tsne::SumArgs za{dchunk, dscalar, chunks};
+    hipLaunchKernelGGL(tsne::tsne_final_sum_kernel, dim3(1), dim3(256), tsne::SUM_CHUNK * 8, h->stream, za);
+    const bool want_kl = last && kl;
+    const tsne::StepArgs sa{dptr, dind, dval, dy[cur], dy[cur ^ 1], dvel, dgain, drs, dscalar, (last && grad_last) ? dgrad : nullptr,
+                            want_kl ? dklrow : nullptr, (int)n, iterations > 0 ? 1 : 0, exaggeration, learning_rate, momentum};
+    hipLaunchKernelGGL(tsne::tsne_step_kernel, dim3(row_grid), dim3(256), 0, h->stream, sa);
+    if (want_kl) {
+      const tsne::SumArgs ka{dklrow, dchunk, n};
+      hipLaunchKernelGGL(tsne::tsne_chunk_sum_kernel, dim3(chunk_grid), dim3(256), tsne::SUM_CHUNK * 8, h->stream, ka);
+      const tsne::SumArgs kf{dchunk, dscalar + 1, chunks};
+      hipLaunchKernelGGL(tsne::tsne_final_sum_kernel, dim3(1), dim3(256), tsne::SUM_CHUNK * 8, h->stream, kf);
+    }
+    HIPCHK(hipGetLastError());
+    if (iterations > 0) cur ^= 1;
+  }
+  HIPCHK(hipEventRecord(h->ev1, h->stream));
+  double scalars[2] = {0.0, 0.0};
+  HIPCHK(hipMemcpyAsync(scalars, dscalar, 16, hipMemcpyDeviceToHost, h->stream));
+  if (iterations > 0) {
+    HIPCHK(hipMemcpyAsync(y, dy[cur], (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(velocity, dvel, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(gains, dgain, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (grad_last) HIPCHK(hipMemcpyAsync(grad_last, dgrad, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipEventElapsedTime(&h->tsne_ms, h->ev0, h->ev1));
+  if (z) *z = scalars[0];
+  if (kl) *kl = scalars[1];
+  return CRBM_OK;
+}
+
+int crbm_tsne_descend_ms(crbm_handle* h, float* ms) {
+  if (!h || !ms) return CRBM_ERR_INVALID;
+  *ms = h->tsne_ms;
+  return CRBM_OK;
 }
 
 }  // extern "C"

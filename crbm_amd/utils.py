@@ -2,10 +2,13 @@
 
 secomo/utils.py:16-47 writes one file per motif through Bio.motifs.jaspar;
 this writer produces the same text layouts without Biopython.  The plotting
-helpers of the reference's utils.py (logos, t-SNE, violin plots) are analysis
-code outside the hot path and are not rebuilt.
+helpers of the reference's utils.py (logos, scatter plots, violin plots) are
+analysis code outside the hot path and are not rebuilt; the embedding behind its
+t-SNE plots is (runTSNE, crbm_amd/tsne.py).
 """
 import os
+
+from .tsne import tsneEmbed
 
 _ALPHABET = ("A", "C", "G", "T")
 
@@ -57,3 +60,11 @@ def saveSites(model, sites, filename, names=None, fformat="bed", name="mot"):
                                 "{:.6g}".format(float(r["prob"])), _STRAND[int(r["strand"])]]))
     with open(filename, "w") as f:
         f.write("".join(line + "\n" for line in lines))
+
+
+def runTSNE(model, seqs, **kw):
+    """t-SNE of the sequences by their motif abundances (utils.py:136-160): the
+    largest hit probability per sequence and motif, motifHitProbs(seqs).max(axis=(2,3)),
+    embedded in the plane by tsneEmbed (whose keyword arguments pass through).
+    `seqs` is the one-hot array or (n, L) letter codes; returns (n, 2) float32."""
+    return tsneEmbed(model, model.motifHitSummary(seqs, position_mean=False)["max"], **kw)

@@ -475,6 +475,48 @@ int crbm_geometry_launches(const crbm_handle* h, int64_t* compiled_in, int64_t* 
 /* Actual bytes of chain state one Gibbs launch reads+writes in HBM. */
 int64_t crbm_gibbs_state_bytes(const crbm_handle* h);
 
+/* ---- t-SNE of row features (utils.py:159-160, the TSNE().fit_transform of runTSNE) ------------------------------
+ * Model-independent: the handle of any model lends its device, its stream and its error string.  Every pointer is
+ * host memory; every call is complete when it returns.  Two components only.  No float atomics and sums in an order
+ * fixed by n alone: the same inputs give the same bits in every run.  (Additive: the ABI version stays.)
+ *
+ * crbm_tsne_neighbors: for every row of X (n, D) float32 its k nearest OTHER rows by
+ *   d2(i,j) = sum_d (x_id - x_jd)^2, float32, d ascending, difference form, no fused multiply-add,
+ * ordered by (d2, j) ascending: idx (n, k) int32 and d2 (n, k) float32.  Exact (brute force): every row sees all n - 1
+ * others.  CRBM_ERR_INVALID: n < 2 or n > 2^30, D < 1 or D > 256, k < 1, k > n - 1, k > 1024 (a wave keeps its list of
+ * k (d2, j) pairs in the LDS), an X that is not finite.
+ *
+ * crbm_tsne_affinities: for every row the beta for which p_j = exp(-beta d2_j) / sum_j exp(-beta d2_j) over its k
+ * distances has entropy log(perplexity) (natural logarithm), and that p (n, k); beta (n).  Bisection in float64 from
+ * beta = 1, doubling or halving while a bound is open, 100 evaluations; the row's smallest d2 is subtracted inside the
+ * exponent.  p is computed at the float32 beta that is returned.  A row that cannot reach the entropy -- all distances
+ * equal, or at least `perplexity` of them tied for the smallest -- ends with a finite beta (2^100 at the most) and p
+ * uniform over the tied.  CRBM_ERR_INVALID: n < 2, k outside [1, min(n - 1, 1024)], a perplexity that is not finite,
+ * not positive or not below k + 1, a distance that is negative or not finite.
+ *
+ * crbm_tsne_descend: `iterations` steps of gradient descent on KL(P || Q), q_ij = w_ij / Z, w_ij = 1 / (1 + |y_i - y_j|^2),
+ * Z = sum_i sum_{j != i} w_ij (exact, all n^2 pairs, float64 over the rows).  P is CSR (indptr (n + 1), indices, values),
+ * kept on the device for the whole call; rows may be empty.  Gradient g_i = 4 (exaggeration A_i - R_i / Z) with
+ * A_i = sum_{j in row i} P_ij w_ij (y_i - y_j) and R_i = sum_{j != i} w_ij^2 (y_i - y_j); update
+ *   gains += 0.2 where velocity * g < 0, else gains *= 0.8, floored at 0.01;
+ *   velocity = momentum * velocity - learning_rate * gains * g;  y += velocity.
+ * y, velocity and gains are (n, 2) float32, read and written.  grad_last (n, 2), kl and z may be null; they receive the
+ * gradient of the last iteration, and KL = sum P_ij log(max(P_ij, e) / max(w_ij / Z, e)), e = 2.2e-16, and Z at the y
+ * that iteration started from.  iterations == 0 evaluates them at y and moves nothing.
+ * CRBM_ERR_INVALID: n < 2 or n > 2^30, iterations < 0, an indptr that does not start at 0 or does not ascend (its last
+ * entry is the number of values), an index outside [0, n).
+ *
+ * crbm_tsne_descend_ms: device time (HIP events) of the iterations of the handle's last crbm_tsne_descend call. */
+int crbm_tsne_neighbors(crbm_handle* h, const float* X, int64_t n, int32_t D, int32_t k,
+                        int32_t* idx, float* d2);
+int crbm_tsne_affinities(crbm_handle* h, const float* d2, int64_t n, int32_t k, float perplexity,
+                         float* p, float* beta);
+int crbm_tsne_descend(crbm_handle* h, int64_t n, const int64_t* indptr, const int32_t* indices,
+                      const float* values, float* y, float* velocity, float* gains, int32_t iterations,
+                      float exaggeration, float learning_rate, float momentum,
+                      float* grad_last, double* kl, double* z);
+int crbm_tsne_descend_ms(crbm_handle* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
