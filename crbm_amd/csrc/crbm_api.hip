@@ -1347,9 +1347,17 @@ int encode_now(crbm_handle* h, const RowSource& src, int start, int cnt, uint32_
   return rc ? rc : check_flags(h);
 }
 
-// rows of a slab whose staged input plus outputs take `bytes_per_row`: the slab budget, CRBM_SLAB_BYTES or 256 MB
+// the slab budget of every sweep: CRBM_SLAB_BYTES or 256 MB, and whether it was set by hand (a sweep over host input
+// then does not cap its slabs at 32 MB)
+struct SlabBudget {
+  size_t bytes;
+  bool was_set;
+};
+SlabBudget slab_budget() { return SlabBudget{(size_t)env_int("CRBM_SLAB_BYTES", 256 << 20), getenv("CRBM_SLAB_BYTES") != nullptr}; }
+
+// rows of a slab whose staged input plus outputs take `bytes_per_row` of the slab budget
 int slab_rows(int n, size_t bytes_per_row) {
-  const size_t budget = (size_t)env_int("CRBM_SLAB_BYTES", 256 << 20);
+  const size_t budget = slab_budget().bytes;
   size_t rows = budget / std::max<size_t>(bytes_per_row, 1);
   if (rows < 1) rows = 1;
   return (int)std::min<size_t>(rows, (size_t)n);
@@ -1358,7 +1366,7 @@ int slab_rows(int n, size_t bytes_per_row) {
 int sweep_slab(const RowSource& src, size_t out_bytes_per_row) {
   const size_t per_row = src.in_bytes_per_row() + out_bytes_per_row;
   int slab = slab_rows(src.n, per_row);
-  if (!src.resident && !getenv("CRBM_SLAB_BYTES")) slab = std::min<size_t>(slab, std::max<size_t>(1, (32u << 20) / std::max<size_t>(per_row, 1)));
+  if (!src.resident && !slab_budget().was_set) slab = std::min<size_t>(slab, std::max<size_t>(1, (32u << 20) / std::max<size_t>(per_row, 1)));
   return slab;
 }
 // tables built and visible to both streams before a sweep starts (the slab tables of a generic DNA model too: a slab on
@@ -1417,19 +1425,35 @@ int sweep_run(crbm_handle* h, const RowSource& src, int slab, int depth, Launch 
   return sweep_finish(h, src);
 }
 
-// ---- the stream sweep (crbm_scan_sites_codes, crbm_scan_histogram_codes) --------------------------------------------
-// What every feature over a stream of T codes (0..3 letters, 4 no letter) shares: a two-stream sweep over segments of
-// window starts (crbm_sweep.h, stream_plan: segment [start, start + cnt) needs letters [start, start + cnt + M - 1), a
-// halo of M - 1 behind its own).  Per segment, on its set's stream: the bytes go up (one per letter), scan_encode_kernel
-// makes letters and validity plane, then the feature's kernels run on the ScanInput the sweep hands it.  A generic DNA
-// model runs the kernels of its slab model, blockIdx.y = slab.  In order:
-//   admit()   the checks on the stream and the model, under the entry point's name; whose kernels run (kms, kjk)
-//   begin()   tables built, the segments planned, stage, letters and validity plane of every set sized for a whole
-//             segment; the feature then sizes what its own kernels write, before run()
-//   run()     launch(set, si, in, start, cnt) enqueues the feature's kernels; collect(...) copies that segment's outputs
-//             out on the set's stream, which the sweep then waits for: the set's buffers are free again.  `timing_env`
-//             set to 1: events around every segment's kernels, their sum on stderr.  At the end both streams are
-//             idle and a code above 4 anywhere in the stream is refused; a failed sweep is drained (sweep_drain).
+// ---- the stream sweep (crbm_scan_*_codes, crbm_variant_effects_codes, crbm_allele_effects_codes) --------------------
+// What every feature over a stream of T codes (0..3 letters, 4 no letter) shares: a two-stream sweep over chunks.  Per
+// chunk, on its set's stream: the staged bytes go up (one per code), scan_encode_kernel makes letters and validity
+// plane, then the feature's kernels run on the ScanInput the sweep hands it.  A generic DNA model runs the kernels of
+// its slab model, blockIdx.y = slab.  The features differ in what a chunk is and where its bytes come from: segments of
+// window starts read straight from the stream (run), or variants whose contexts the host gathers first (the stage
+// callables of variant_effects_any and allele_effects_any).  In order:
+//   admit()        the checks on the stream and the model, under the entry point's name; whose kernels run (kms, kjk)
+//   begin()        for the segment sweeps: tables built, the segments planned (stream_plan: segment [start, start + cnt)
+//                  needs letters [start, start + cnt + M - 1), a halo of M - 1 behind its own), size_inputs
+//   size_inputs()  stage, letters and validity plane of every set, sized for a whole chunk; the feature then sizes what
+//                  its own kernels write -- all of it before run_chunks, while neither stream runs
+//   run_chunks()   walks (n, slab) as run_slabs does.  stage(si, c) names the chunk's host bytes and what is made of
+//                  them (Chunk); launch(set, si, in, start, cnt) enqueues the feature's kernels; collect(...) copies that
+//                  chunk's outputs out on the set's stream, which the sweep then waits for: the set's buffers are free
+//                  again.  `timing_env` set to 1: events around every chunk's kernels, their sum on stderr, counted in
+//                  `unit`.  At the end both streams are idle and a code above 4 anywhere in what was staged is refused
+//                  (a feature that has checked the stream on the host pays one 4-byte copy for a flag that is never
+//                  raised); a failed sweep is drained (sweep_drain).
+//   run()          run_chunks over the plan's segments, staged where they lie in `codes`
+const char* const kBadStreamCode = "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)";
+// the refusal of the sweep's epilogue, on the host: for what must be refused before anything is launched
+int check_stream_codes(crbm_handle* h, const uint8_t* codes, int64_t T) {
+  unsigned bad = 0;
+  for (int64_t i = 0; i < T; ++i) bad |= codes[i] > 4 ? 1u : 0u;
+  ARGCHK(!bad, kBadStreamCode);
+  return CRBM_OK;
+}
+
 struct StreamSweep {
   crbm_handle* h;
   const char* api;                       // the entry point: named in its refusals and in its timing line
@@ -1437,6 +1461,15 @@ struct StreamSweep {
   const JitKernels* kjk = nullptr;
   int M = 0, S = 0, nslab = 0;
   StreamPlan plan{};
+
+  // one chunk as its stage() leaves it; start and cnt come in as run_slabs counts them
+  struct Chunk {
+    int start, cnt;                      // what launch and collect are told
+    const uint8_t* bytes;                // host bytes to copy up, `up` of them
+    size_t up;
+    long n, layout_starts;               // staged codes to encode; scan_layout(n, layout_starts)
+    int32_t starts;                      // ScanInput::starts
+  };
 
   int admit(const uint8_t* codes, int64_t T) {
     const std::string who = std::string(api) + ": ";
@@ -1451,21 +1484,37 @@ struct StreamSweep {
     return CRBM_OK;
   }
 
-  int begin(int64_t T) {                 // T >= M
-    const int rc = sweep_begin(h);
-    if (rc) return rc;
-    plan = stream_plan((long)T, M, nslab, (size_t)env_int("CRBM_SLAB_BYTES", 256 << 20), getenv("CRBM_SLAB_BYTES") != nullptr);
-    for (int i = 0; i < plan.nsets; ++i) {
+  int size_inputs(int nsets, size_t staged_bytes, const ScanLayout& full) {
+    for (int i = 0; i < nsets; ++i) {
       const SweepSet set = sweep_set(h, i);
-      HIPCHK(set.stage->ensure(((size_t)plan.seg + M - 1 + 3) / 4));
-      HIPCHK(set.letters->ensure((size_t)plan.full.letter_words));
-      HIPCHK(set.own->scan_valid.ensure((size_t)plan.full.valid_words));
+      HIPCHK(set.stage->ensure((staged_bytes + 3) / 4));
+      HIPCHK(set.letters->ensure((size_t)full.letter_words));
+      HIPCHK(set.own->scan_valid.ensure((size_t)full.valid_words));
     }
     return CRBM_OK;
   }
 
-  template <class Launch, class Collect>
-  int run(const uint8_t* codes, const char* timing_env, Launch launch, Collect collect) {
+  int begin(int64_t T) {                 // T >= M
+    const int rc = sweep_begin(h);
+    if (rc) return rc;
+    const SlabBudget budget = slab_budget();
+    plan = stream_plan((long)T, M, nslab, budget.bytes, budget.was_set);
+    return size_inputs(plan.nsets, (size_t)plan.seg + M - 1, plan.full);
+  }
+
+  // what every stream kernel reads of a chunk encoded into `set`: the one place a ScanInput is filled
+  ScanInput input(const SweepSet& set, int32_t starts, int32_t tiles) const {
+    ScanInput a;
+    a.tables = h->big() ? h->d_slab_tables : h->d_tables;
+    a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
+    a.starts = starts; a.tiles = tiles; a.table_stride = kms->TABLES_ALL;
+    if (h->big()) a.plan = slab_plan(h);
+    else { a.plan.Ks = h->K; a.plan.K = h->K; a.plan.last_k0 = 0; }
+    return a;
+  }
+
+  template <class Stage, class Launch, class Collect>
+  int run_chunks(int n, int slab, const char* timing_env, const char* unit, Stage stage, Launch launch, Collect collect) {
     const bool timing = env_int(timing_env, 0) != 0;
     struct Events {                      // destroyed on every way out
       hipEvent_t e[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
@@ -1477,50 +1526,49 @@ struct StreamSweep {
     } events;
     auto& tev = events.e;
     double device_ms = 0.0;
-    int segments = 0;
+    int timed = 0;
     if (timing)
       for (int i = 0; i < 2; ++i)
         for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
     ScanInput in[2];
-    const int rc = run_slabs(plan.starts_all, plan.seg, 2,
+    Chunk chunk[2];
+    const int rc = run_slabs(n, slab, 2,
       [&](int, int si, int start, int cnt) -> int {
         const SweepSet set = sweep_set(h, si);
-        const long n = (long)cnt + M - 1;                // (start + cnt <= T - M + 1: the halo is inside the stream)
-        const ScanLayout l = scan_layout(n, cnt);
-        HIPCHK(hipMemcpyAsync(set.stage->p, codes + start, (size_t)n, hipMemcpyHostToDevice, set.st));
+        Chunk& c = chunk[si];
+        c = Chunk{start, cnt, nullptr, 0, 0, 0, 0};
+        int r = stage(si, c);
+        if (r) return r;
+        const ScanLayout l = scan_layout(c.n, c.layout_starts);
+        HIPCHK(hipMemcpyAsync(set.stage->p, c.bytes, c.up, hipMemcpyHostToDevice, set.st));
         if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
         ScanEncodeArgs e;
         e.codes = reinterpret_cast<const unsigned char*>(set.stage->p);
         e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;
-        e.n = n; e.valid_words = l.valid_words;
+        e.n = c.n; e.valid_words = l.valid_words;
         hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
         HIPCHK(hipGetLastError());
-        ScanInput& a = in[si];
-        a.tables = h->big() ? h->d_slab_tables : h->d_tables;
-        a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
-        a.starts = cnt; a.tiles = l.tiles; a.table_stride = kms->TABLES_ALL;
-        if (h->big()) a.plan = slab_plan(h);
-        else { a.plan.Ks = h->K; a.plan.K = h->K; a.plan.last_k0 = 0; }
-        const int r = launch(set, si, a, start, cnt);
+        in[si] = input(set, c.starts, l.tiles);
+        r = launch(set, si, in[si], c.start, c.cnt);
         if (!r && timing) HIPCHK(hipEventRecord(tev[si][1], set.st));
         return r;
       },
-      [&](int, int si, int start, int cnt) -> int {
+      [&](int, int si, int, int) -> int {
         const SweepSet set = sweep_set(h, si);
-        const int r = collect(set, si, in[si], start, cnt);
+        const int r = collect(set, si, in[si], chunk[si].start, chunk[si].cnt);
         if (r) return r;
         HIPCHK(hipStreamSynchronize(set.st));
         if (timing) {
           float ms = 0.f;
           HIPCHK(hipEventElapsedTime(&ms, tev[si][0], tev[si][1]));
           device_ms += ms;
-          ++segments;
+          ++timed;
         }
         return CRBM_OK;
       },
       [&] { sweep_drain(h); });
     if (rc) return rc;
-    if (timing) fprintf(stderr, "%s: kernels %.3f ms over %d segments\n", api, device_ms, segments);
+    if (timing) fprintf(stderr, "%s: kernels %.3f ms over %d %s\n", api, device_ms, timed, unit);
     HIPCHK(hipStreamSynchronize(h->stream2));
     HIPCHK(hipStreamSynchronize(h->stream));
     uint32_t flags = 0;
@@ -1529,9 +1577,20 @@ struct StreamSweep {
     if (flags) {
       HIPCHK(hipMemsetAsync(h->d_flags, 0, sizeof(uint32_t), h->stream));
       HIPCHK(hipStreamSynchronize(h->stream));
-      return fail(h, CRBM_ERR_INVALID, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
+      return fail(h, CRBM_ERR_INVALID, kBadStreamCode);
     }
     return CRBM_OK;
+  }
+
+  template <class Launch, class Collect>
+  int run(const uint8_t* codes, const char* timing_env, Launch launch, Collect collect) {
+    return run_chunks(plan.starts_all, plan.seg, timing_env, "segments",
+      [&](int, Chunk& c) -> int {        // (start + cnt <= T - M + 1: the halo is inside the stream)
+        c.bytes = codes + c.start; c.n = (long)c.cnt + M - 1; c.up = (size_t)c.n;
+        c.layout_starts = c.cnt; c.starts = c.cnt;
+        return CRBM_OK;
+      },
+      launch, collect);
   }
 };
 
@@ -2786,7 +2845,8 @@ int scan_records_any(crbm_handle* h, const uint8_t* codes, int64_t T, const int6
   const size_t words = off_counts + (want_counts ? (size_t)nrec * 5 : 0);
   std::vector<unsigned long long> acc(words, 0ull);
   if (T < M) {                           // no window anywhere
-    for (int64_t i = 0; i < T; ++i) ARGCHK(codes[i] <= 4, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
+    rc = check_stream_codes(h, codes, T);
+    if (rc) return rc;
     if (want_counts)
       for (int64_t r = 0; r < nrec; ++r)
         for (int64_t i = rec_start[r]; i < rec_start[r + 1] - 1; ++i)
@@ -2829,10 +2889,9 @@ int scan_records_any(crbm_handle* h, const uint8_t* codes, int64_t T, const int6
 }
 
 // ---- variant effects (crbm_variant_effects_codes) -------------------------------------------------------------------
-// A two-stream sweep over the variant list in chunks (crbm_sweep.h, variant_plan).  Everything that can be refused is
-// refused on the host before anything is launched: outputs are then left as they were.  Per chunk, on its set's
-// stream: the host gathers the contexts (crbm_sweep.h, gather_contexts) and the alt bytes into the set's host buffer,
-// one copy takes them up; scan_encode_kernel makes letters and validity plane of the contexts,
+// A StreamSweep whose chunks are variants (crbm_sweep.h, variant_plan).  Everything that can be refused is refused on
+// the host before anything is launched: outputs are then left as they were.  A chunk's stage gathers the contexts
+// (crbm_sweep.h, gather_contexts) and the alt bytes into the set's host buffer, which the sweep copies up and encodes;
 // crbm_variant_effects leaves per_motif [cnt][K] (set.oa) and the valid windows, variant_combine_kernel forms dfe
 // (set.ob); the outputs asked for are copied straight into the caller's arrays at the chunk's offset.  Every set owns
 // what it writes, sized for a whole chunk before the sweep starts.  CRBM_VARIANT_TIMING=1: tools/bench_variants.py.
@@ -2845,10 +2904,10 @@ int variant_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t
   ARGCHK(nvar >= 0 && nvar <= (int64_t)INT32_MAX, "nvar must lie in [0, 2^31 - 1]");
   if (nvar == 0) return CRBM_OK;
   ARGCHK(pos && alt, "null argument");
+  rc = check_stream_codes(h, codes, T);
+  if (rc) return rc;
   {
     unsigned bad = 0;
-    for (int64_t i = 0; i < T; ++i) bad |= codes[i] > 4 ? 1u : 0u;
-    ARGCHK(!bad, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
     for (int64_t i = 0; i < nvar; ++i) bad |= (pos[i] < 0 || pos[i] >= T ? 1u : 0u) | (alt[i] > 3 ? 2u : 0u);
     ARGCHK(!(bad & 1u), "crbm_variant_effects_codes: every pos must lie in [0, T)");
     ARGCHK(!(bad & 2u), "crbm_variant_effects_codes: every alt must be a letter code 0..3");
@@ -2856,65 +2915,36 @@ int variant_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t
   rc = sweep_begin(h);
   if (rc) return rc;
   const int M = sw.M, K = h->K, nslab = sw.nslab;
-  const VariantPlan vp = variant_plan((long)nvar, M, K, (size_t)env_int("CRBM_SLAB_BYTES", 256 << 20),
-                                      getenv("CRBM_SLAB_BYTES") != nullptr);
+  const SlabBudget budget = slab_budget();
+  const VariantPlan vp = variant_plan((long)nvar, M, K, budget.bytes, budget.was_set);
   const int CW = vp.CW;
   auto ctx_bytes = [&](int cnt) { return ((size_t)cnt * CW + 3) & ~(size_t)3; };   // the alt bytes follow the contexts
   std::vector<uint8_t> host[2];
-  for (int i = 0; i < vp.nsets; ++i) {                     // everything both streams write, at its size, before either starts
+  for (int i = 0; i < vp.nsets; ++i) host[i].resize(ctx_bytes(vp.chunk) + (size_t)vp.chunk);
+  rc = sw.size_inputs(vp.nsets, host[0].size(), vp.full);
+  if (rc) return rc;
+  for (int i = 0; i < vp.nsets; ++i) {                     // what both streams write, at its size, before either starts
     const SweepSet set = sweep_set(h, i);
-    host[i].resize(ctx_bytes(vp.chunk) + (size_t)vp.chunk);
-    HIPCHK(set.stage->ensure((host[i].size() + 3) / 4));
-    HIPCHK(set.letters->ensure((size_t)vp.full.letter_words));
-    HIPCHK(set.own->scan_valid.ensure((size_t)vp.full.valid_words));
     HIPCHK(set.oa->ensure((size_t)vp.chunk * K));
     HIPCHK(set.ob->ensure((size_t)vp.chunk));
     HIPCHK(set.own->var_windows.ensure((size_t)vp.chunk));
   }
-  const bool timing = env_int("CRBM_VARIANT_TIMING", 0) != 0;
-  struct Events {                        // destroyed on every way out
-    hipEvent_t e[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    ~Events() {
-      for (auto& set : e)
-        for (hipEvent_t ev : set)
-          if (ev) (void)hipEventDestroy(ev);
-    }
-  } events;
-  auto& tev = events.e;
-  double device_ms = 0.0;
-  int chunks = 0;
-  if (timing)
-    for (int i = 0; i < 2; ++i)
-      for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
-  rc = run_slabs((int)nvar, vp.chunk, 2,
-    [&](int, int si, int start, int cnt) -> int {
-      const SweepSet set = sweep_set(h, si);
+  return sw.run_chunks((int)nvar, vp.chunk, "CRBM_VARIANT_TIMING", "chunks",
+    [&](int si, StreamSweep::Chunk& c) -> int {
       uint8_t* ctx = host[si].data();
-      uint8_t* alts = ctx + ctx_bytes(cnt);
-      gather_contexts(codes, T, pos + start, cnt, M, ctx);
-      std::memcpy(alts, alt + start, (size_t)cnt);
-      const size_t up = ctx_bytes(cnt) + (size_t)cnt;
-      HIPCHK(hipMemcpyAsync(set.stage->p, ctx, up, hipMemcpyHostToDevice, set.st));
-      if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
-      const long n = (long)cnt * CW;
-      const ScanLayout l = scan_layout(n, cnt);
+      gather_contexts(codes, T, pos + c.start, c.cnt, M, ctx);
+      std::memcpy(ctx + ctx_bytes(c.cnt), alt + c.start, (size_t)c.cnt);
+      c.bytes = ctx; c.up = ctx_bytes(c.cnt) + (size_t)c.cnt;
+      c.n = (long)c.cnt * CW; c.layout_starts = c.cnt; c.starts = (int32_t)(c.n - M + 1);
+      return CRBM_OK;
+    },
+    [&](const SweepSet& set, int, const ScanInput& in, int, int cnt) -> int {
       const unsigned char* staged = reinterpret_cast<const unsigned char*>(set.stage->p);
-      ScanEncodeArgs e;
-      e.codes = staged;
-      e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;   // (no code above 4: checked above)
-      e.n = n; e.valid_words = l.valid_words;
-      hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
-      HIPCHK(hipGetLastError());
-      VariantArgs a{};
-      a.tables = h->big() ? h->d_slab_tables : h->d_tables;
-      a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
-      a.starts = (int32_t)(n - M + 1); a.tiles = l.tiles; a.table_stride = sw.kms->TABLES_ALL;
-      if (h->big()) a.plan = slab_plan(h);
-      else { a.plan.Ks = K; a.plan.K = K; a.plan.last_k0 = 0; }
+      VariantArgs a{in};
       a.alt = staged + ctx_bytes(cnt);
       a.per_motif = set.oa->p; a.windows = set.own->var_windows.p;
       a.cnt = cnt; a.pad_ = 0;
-      const unsigned gx = (unsigned)std::max(1, std::min((l.tiles + 3) / 4, std::max(1, h->num_cu * 8 / nslab)));
+      const unsigned gx = (unsigned)std::max(1, std::min((in.tiles + 3) / 4, std::max(1, h->num_cu * 8 / nslab)));
       HIPCHK(jit_launch(sw.kjk->variant_effects, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(*sw.kms), set.st));
       if (dfe) {
         VariantCombineArgs c;
@@ -2923,40 +2953,25 @@ int variant_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t
         hipLaunchKernelGGL(variant_combine_kernel, dim3(grid_for(cnt, 256, h->num_cu * 8)), dim3(256), 0, set.st, c);
         HIPCHK(hipGetLastError());
       }
-      if (timing) HIPCHK(hipEventRecord(tev[si][1], set.st));
       return CRBM_OK;
     },
-    [&](int, int si, int start, int cnt) -> int {
-      const SweepSet set = sweep_set(h, si);
+    [&](const SweepSet& set, int, const ScanInput&, int start, int cnt) -> int {
       const size_t at = (size_t)start;
       if (dfe) HIPCHK(hipMemcpyAsync(dfe + at, set.ob->p, (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost, set.st));
       if (per_motif) HIPCHK(hipMemcpyAsync(per_motif + at * K, set.oa->p, (size_t)cnt * K * sizeof(float), hipMemcpyDeviceToHost, set.st));
       if (windows) HIPCHK(hipMemcpyAsync(windows + at, set.own->var_windows.p, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, set.st));
-      HIPCHK(hipStreamSynchronize(set.st));
-      if (timing) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, tev[si][0], tev[si][1]));
-        device_ms += ms;
-        ++chunks;
-      }
       return CRBM_OK;
-    },
-    [&] { sweep_drain(h); });
-  if (rc) return rc;
-  if (timing) fprintf(stderr, "crbm_variant_effects_codes: kernels %.3f ms over %d chunks\n", device_ms, chunks);
-  HIPCHK(hipStreamSynchronize(h->stream2));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return CRBM_OK;
+    });
 }
 
 // ---- allele effects (crbm_allele_effects_codes) ---------------------------------------------------------------------
-// variant_effects_any for alleles of any length: a two-stream sweep over the chunks of allele_plan (crbm_sweep.h), which
-// hold different numbers of variants -- run_slabs walks the chunks one at a time.  Everything that can be refused is
-// refused on the host before anything is launched.  Per chunk, on its set's stream: the host gathers both haplotypes of
-// every variant and their table entries (gather_haplotypes) into the set's host buffer, one copy takes them up;
-// scan_encode_kernel makes letters and validity plane, crbm_allele_effects leaves per_motif [cnt][K] (set.oa) and the
-// valid windows [cnt][2], allele_combine_kernel forms dfe (set.ob); the outputs asked for are copied straight into the
-// caller's arrays.  Every set owns what it writes, sized for the largest chunk before the sweep starts.
+// variant_effects_any for alleles of any length: a StreamSweep over the chunks of allele_plan (crbm_sweep.h), which hold
+// different numbers of variants -- the sweep walks the chunks one at a time and the stage names each chunk's variants.
+// Everything that can be refused is refused on the host before anything is launched.  A chunk's stage gathers both
+// haplotypes of every variant and their table entries (gather_haplotypes) into the set's host buffer, which the sweep
+// copies up and encodes; crbm_allele_effects leaves per_motif [cnt][K] (set.oa) and the valid windows [cnt][2],
+// allele_combine_kernel forms dfe (set.ob); the outputs asked for are copied straight into the caller's arrays.  Every
+// set owns what it writes, sized for the largest chunk before the sweep starts.
 // CRBM_ALLELE_TIMING=1: tools/bench_alleles.py.
 int allele_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t nvar, const int64_t* pos, const int32_t* ref_len,
                        const int64_t* alt_off, const uint8_t* alt_codes, float* dfe, float* per_motif, int32_t* windows) {
@@ -2967,10 +2982,10 @@ int allele_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t 
   ARGCHK(nvar >= 0 && nvar <= (int64_t)INT32_MAX, "nvar must lie in [0, 2^31 - 1]");
   if (nvar == 0) return CRBM_OK;
   ARGCHK(pos && ref_len && alt_off, "null argument");
+  rc = check_stream_codes(h, codes, T);
+  if (rc) return rc;
   {
     unsigned bad = 0;
-    for (int64_t i = 0; i < T; ++i) bad |= codes[i] > 4 ? 1u : 0u;
-    ARGCHK(!bad, "stream codes must lie in 0..4 (0..3 = A,C,G,T; 4 = no letter)");
     ARGCHK(alt_off[0] == 0, "crbm_allele_effects_codes: alt_off must ascend from 0");
     for (int64_t i = 0; i < nvar; ++i) {
       const int64_t A = alt_off[i + 1] - alt_off[i];
@@ -2990,40 +3005,23 @@ int allele_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t 
   rc = sweep_begin(h);
   if (rc) return rc;
   const int M = sw.M, K = h->K, nslab = sw.nslab;
-  const AllelePlan ap = allele_plan((long)nvar, ref_len, alt_off, M, K, (size_t)env_int("CRBM_SLAB_BYTES", 256 << 20),
-                                    getenv("CRBM_SLAB_BYTES") != nullptr);
+  const SlabBudget budget = slab_budget();
+  const AllelePlan ap = allele_plan((long)nvar, ref_len, alt_off, M, K, budget.bytes, budget.was_set);
   auto code_bytes = [](long n) { return ((size_t)n + 15) & ~(size_t)15; };         // the table follows the codes
   std::vector<uint8_t> host[2];
-  for (int i = 0; i < ap.nsets; ++i) {                     // everything both streams write, at its size, before either starts
+  for (int i = 0; i < ap.nsets; ++i) host[i].resize(code_bytes(ap.max_codes) + (size_t)ap.max_cnt * sizeof(AlleleEntry));
+  rc = sw.size_inputs(ap.nsets, host[0].size(), ap.full);
+  if (rc) return rc;
+  for (int i = 0; i < ap.nsets; ++i) {                     // what both streams write, at its size, before either starts
     const SweepSet set = sweep_set(h, i);
-    host[i].resize(code_bytes(ap.max_codes) + (size_t)ap.max_cnt * sizeof(AlleleEntry));
-    HIPCHK(set.stage->ensure((host[i].size() + 3) / 4));
-    HIPCHK(set.letters->ensure((size_t)ap.full.letter_words));
-    HIPCHK(set.own->scan_valid.ensure((size_t)ap.full.valid_words));
     HIPCHK(set.oa->ensure((size_t)ap.max_cnt * K));
     HIPCHK(set.ob->ensure((size_t)ap.max_cnt));
     HIPCHK(set.own->var_windows.ensure((size_t)2 * ap.max_cnt));
   }
-  const bool timing = env_int("CRBM_ALLELE_TIMING", 0) != 0;
-  struct Events {                        // destroyed on every way out
-    hipEvent_t e[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    ~Events() {
-      for (auto& set : e)
-        for (hipEvent_t ev : set)
-          if (ev) (void)hipEventDestroy(ev);
-    }
-  } events;
-  auto& tev = events.e;
-  double device_ms = 0.0;
-  int chunks = 0;
-  if (timing)
-    for (int i = 0; i < 2; ++i)
-      for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
-  rc = run_slabs((int)ap.cuts.size() - 1, 1, 2,
-    [&](int, int si, int chunk, int) -> int {
-      const SweepSet set = sweep_set(h, si);
-      const int64_t start = ap.cuts[chunk];
-      const int cnt = (int)(ap.cuts[chunk + 1] - start);
+  return sw.run_chunks((int)ap.cuts.size() - 1, 1, "CRBM_ALLELE_TIMING", "chunks",
+    [&](int si, StreamSweep::Chunk& c) -> int {            // (comes in as chunk c.start of the plan)
+      const int64_t start = ap.cuts[c.start];
+      const int cnt = (int)(ap.cuts[c.start + 1] - start);
       uint8_t* hap = host[si].data();
       // (the table's place does not depend on the codes gathered: sized from the plan's arithmetic, checked below)
       long n = 0;
@@ -3031,24 +3029,15 @@ int allele_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t 
       AlleleEntry* table = reinterpret_cast<AlleleEntry*>(hap + code_bytes(n));
       const long wrote = gather_haplotypes(codes, T, pos + start, ref_len + start, alt_off + start, alt_codes, cnt, M, hap, table);
       if (wrote != n || n > ap.max_codes || cnt > ap.max_cnt) return fail(h, CRBM_ERR_INVALID, "crbm_allele_effects_codes: a chunk outgrew its plan");
-      const size_t up = code_bytes(n) + (size_t)cnt * sizeof(AlleleEntry);
-      HIPCHK(hipMemcpyAsync(set.stage->p, hap, up, hipMemcpyHostToDevice, set.st));
-      if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
-      const ScanLayout l = scan_layout(n, n);
+      c.start = (int)start; c.cnt = cnt;
+      c.bytes = hap; c.up = code_bytes(n) + (size_t)cnt * sizeof(AlleleEntry);
+      c.n = n; c.layout_starts = n; c.starts = (int32_t)n;
+      return CRBM_OK;
+    },
+    [&](const SweepSet& set, int, const ScanInput& in, int, int cnt) -> int {
       const unsigned char* staged = reinterpret_cast<const unsigned char*>(set.stage->p);
-      ScanEncodeArgs e;
-      e.codes = staged;
-      e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;   // (no code above 4: checked above)
-      e.n = n; e.valid_words = l.valid_words;
-      hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
-      HIPCHK(hipGetLastError());
-      AlleleArgs a{};
-      a.tables = h->big() ? h->d_slab_tables : h->d_tables;
-      a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
-      a.starts = (int32_t)n; a.tiles = l.tiles; a.table_stride = sw.kms->TABLES_ALL;
-      if (h->big()) a.plan = slab_plan(h);
-      else { a.plan.Ks = K; a.plan.K = K; a.plan.last_k0 = 0; }
-      a.table = reinterpret_cast<const AlleleEntry*>(staged + code_bytes(n));
+      AlleleArgs a{in};
+      a.table = reinterpret_cast<const AlleleEntry*>(staged + code_bytes(in.starts));
       a.per_motif = set.oa->p; a.windows = set.own->var_windows.p;
       a.cnt = cnt; a.pad_ = 0;
       // a wave per variant, four waves a block
@@ -3061,30 +3050,15 @@ int allele_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t 
         hipLaunchKernelGGL(allele_combine_kernel, dim3(grid_for(cnt, 256, h->num_cu * 8)), dim3(256), 0, set.st, c);
         HIPCHK(hipGetLastError());
       }
-      if (timing) HIPCHK(hipEventRecord(tev[si][1], set.st));
       return CRBM_OK;
     },
-    [&](int, int si, int chunk, int) -> int {
-      const SweepSet set = sweep_set(h, si);
-      const size_t at = (size_t)ap.cuts[chunk], cnt = (size_t)(ap.cuts[chunk + 1] - ap.cuts[chunk]);
+    [&](const SweepSet& set, int, const ScanInput&, int start, int n) -> int {
+      const size_t at = (size_t)start, cnt = (size_t)n;
       if (dfe) HIPCHK(hipMemcpyAsync(dfe + at, set.ob->p, cnt * sizeof(float), hipMemcpyDeviceToHost, set.st));
       if (per_motif) HIPCHK(hipMemcpyAsync(per_motif + at * K, set.oa->p, cnt * K * sizeof(float), hipMemcpyDeviceToHost, set.st));
       if (windows) HIPCHK(hipMemcpyAsync(windows + 2 * at, set.own->var_windows.p, 2 * cnt * sizeof(int32_t), hipMemcpyDeviceToHost, set.st));
-      HIPCHK(hipStreamSynchronize(set.st));
-      if (timing) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, tev[si][0], tev[si][1]));
-        device_ms += ms;
-        ++chunks;
-      }
       return CRBM_OK;
-    },
-    [&] { sweep_drain(h); });
-  if (rc) return rc;
-  if (timing) fprintf(stderr, "crbm_allele_effects_codes: kernels %.3f ms over %d chunks\n", device_ms, chunks);
-  HIPCHK(hipStreamSynchronize(h->stream2));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return CRBM_OK;
+    });
 }
 
 // ---- in-silico mutagenesis (crbm_mutagenesis*) ----------------------------------------------------------------------
