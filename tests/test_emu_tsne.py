@@ -2,7 +2,8 @@
 a stand-alone program built here and run directly (no preloaded runtime).  Neighbours equal tests/tsne_reference.py bit for
 bit; affinities and one descent step are held to it at the tolerances of tests/test_gpu_tsne.py; several grid and block
 sizes give the same bits; what the entry points refuse is refused (the checks are the header's); guard words around
-every output must be intact."""
+every output must be intact.  The edges of the row load, the candidate tile and the list's shift, and one descent step
+with three tiles per slice (n = 16 385), run here with the LDS and every buffer sized to the byte."""
 import os
 import subprocess
 
@@ -89,6 +90,34 @@ def test_neighbours_equal_the_reference_bit_for_bit(exe, tmp_path, n, D, k, eigh
             assert np.array_equal(other[0], idx) and np.array_equal(other[1].view(np.uint32), d2.view(np.uint32)), (grid, threads)
 
 
+EDGE_SHAPES = [(130, D, 65) for D in (64, 65, 128, 129)] + [(n, 3, n - 1) for n in (63, 64, 128)]
+LIMIT_CASES = [(n, D, k, False, grid, threads) for n, D, k in EDGE_SHAPES for grid, threads in ((2, 128), (3, 512))] + [
+    (70, 256, 11, False, 2, 128), (70, 255, 69, False, 3, 512),             # the longest row; odd D: the stride equals D
+    (140, 2, 135, False, 2, 128), (140, 2, 135, False, 3, 512),             # three shift steps, the last of six entries
+    (140, 1, 130, "descending", 3, 512), (200, 1, 65, "descending", 2, 128)]  # every candidate shifts the whole list
+
+
+@pytest.mark.parametrize("n,D,k,data,grid,threads", LIMIT_CASES)
+def test_neighbours_at_the_edges_of_the_row_load_the_tile_and_the_shift(exe, tmp_path, n, D, k, data, grid, threads):
+    """The emulator sizes the LDS to the byte, so here an overrun of the row load (D on either side of one and two
+    64-lane passes, D = 256 and 255), of the candidate tile (n = 63, 64, 128) or of knn_insert's shift (k = 65: a last
+    step of one entry; k above 128) shows; two and eight waves per block.
+
+    Times on the CPU machine (8 cores): the slowest case of this file before these was [257-10-90-False] at 28 s; the
+    slowest new ones are (200, 1, 65, descending) at 14 s, (140, *, 13x) at 12 to 13 s and (128, 3, 127) at 10 s, the
+    others 2 to 7 s.
+
+    k near 1024 is not affordable here: every shift step of knn_insert is two emulated wave barriers, each a pthread
+    barrier of 64 OS threads, about 0.25 ms a step.  On descending rows (n, k) = (130, 65), (140, 130), (280, 260) took
+    6.5, 13 and 76 s for about 26, 50 and 350 thousand steps: linear in the steps, so the emulator is slow there, not
+    stalled.  (1100, 256, 1024) is some 10^7 steps, most of an hour.  tests/test_gpu_tsne.py is the only cover of k
+    above 135 and of the four-wave launch."""
+    X = R.descending_rows(n) if data == "descending" else R.feature_rows(n, D, seed=n + D, eighths=data)
+    idx, d2 = knn(exe, tmp_path, X, k, grid=grid, threads=threads)
+    ridx, rd2 = R.neighbors(X, k)
+    assert np.array_equal(idx, ridx) and np.array_equal(d2.view(np.uint32), rd2.view(np.uint32))
+
+
 def check_affinities(d2, perplexity, p, beta):
     """the three conditions of the affinity kernel, shared with tests/test_gpu_tsne.py"""
     k = d2.shape[1]
@@ -150,24 +179,50 @@ def step_inputs(n, scale, seed, k=None, empty_row=False):
     return (indptr, indices, values), R.csr_to_dense(n, indptr, indices, values.astype(np.float64)), y, vel, gains
 
 
+_LARGE = {}
+
+
+def large_inputs(n, scale):
+    """sparse P with an empty row, distinct random y at `scale`, velocity and gains as in step_inputs, and the float64
+    reference at exaggeration 1 (blocked, some seconds at n = 16 385) -- computed once and never written to"""
+    if (n, scale) not in _LARGE:
+        rng = np.random.default_rng(n + (scale > 1.0))
+        csr = R.sparse_joint(n, seed=n, empty_row=300)
+        y = (scale * rng.standard_normal((n, 2))).astype(np.float32)
+        assert np.unique(y, axis=0).shape[0] == n
+        vel = (scale * 0.1 * rng.standard_normal((n, 2))).astype(np.float32)
+        gains = rng.choice(np.array([0.01, 0.5, 1.0, 1.2, 2.4], np.float32), size=(n, 2))
+        _LARGE[n, scale] = (csr, y, vel, gains, R.kl_gradient_csr(csr, y, 1.0))
+    return _LARGE[n, scale]
+
+
 def grad_bound(ref, ex):
     """1e-4 of the largest 4 exaggeration |A_i| + 4 |R_i| / Z: the two terms of the gradient cancel, and it carries their rounding"""
     return 1e-4 * (4.0 * ex * np.abs(ref["A"]) + 4.0 * np.abs(ref["R"]) / ref["z"]).max()
 
 
-def settle(P, y, vel, ex):
+def reference_at(ref, y, ex):
+    """`ref`: the dict of tsne_reference.kl_gradient (or _csr, _grouped) at y and ex, or a callable (y float64, ex) that gives it"""
+    return ref(y.astype(np.float64), ex) if callable(ref) else ref
+
+
+def dense_reference(P):
+    return lambda y, ex: R.kl_gradient(P, y, ex)
+
+
+def settle(ref, y, vel, ex):
     """the velocity with an exact zero wherever the reference's gradient is within four bounds of zero: there the sign of
     velocity * g would hang on the gradient's rounding; a zero product is no such decision (0 < 0 is false whatever g is)"""
-    ref = R.kl_gradient(P, y.astype(np.float64), ex)
+    ref = reference_at(ref, y, ex)
     out = vel.copy()
     out[np.abs(ref["grad"]) <= 4.0 * grad_bound(ref, ex)] = 0.0
     assert (out != 0).mean() > 0.9
     return out
 
 
-def check_step(got, P, y, vel, gains, ex, lr, mom):
+def check_step(got, ref, y, vel, gains, ex, lr, mom):
     """one step against the reference at the tolerances of the issue; returns the gradient's error as a share of its bound"""
-    ref = R.kl_gradient(P, y.astype(np.float64), ex)
+    ref = reference_at(ref, y, ex)
     bound = grad_bound(ref, ex)
     err = np.abs(got["grad"] - ref["grad"]).max()
     assert err <= bound, (err, bound)
@@ -192,15 +247,32 @@ def test_one_descent_step(exe, tmp_path, n, k, scale, ex):
     csr, P, y, vel, gains = step_inputs(n, scale, seed=n, k=k, empty_row=(n == 257 and ex == 1.0))
     if k is not None:
         assert np.unique(np.diff(csr[0])).size > 1                                   # rows of unequal length
-    vel = settle(P, y, vel, ex)
+    vel = settle(dense_reference(P), y, vel, ex)
     got = descend(exe, tmp_path, csr, y, vel, gains, 1, ex, 50.0, 0.5)
-    check_step(got, P, y, vel, gains, ex, 50.0, 0.5)
+    check_step(got, dense_reference(P), y, vel, gains, ex, 50.0, 0.5)
     if n == 257:
         for grid, threads in ((1, 64), (5, 256), (3, 512)):
             other = descend(exe, tmp_path, csr, y, vel, gains, 1, ex, 50.0, 0.5, grid=grid, threads=threads)
             for key in ("y", "velocity", "gains", "grad"):
                 assert np.array_equal(other[key].view(np.uint32), got[key].view(np.uint32)), (key, grid, threads)
             assert other["kl"] == got["kl"] and other["z"] == got["z"]
+
+
+@pytest.mark.parametrize("grid,threads", [(2, 256), (3, 128)])
+def test_one_descent_step_with_three_tiles_per_slice(exe, tmp_path, grid, threads):
+    """n = 16 385 (tests/test_gpu_tsne.py has the shape's facts): the tile loop of tsne_repulsion_kernel, the short last
+    slice and the one-point last tile with every buffer sized exactly; with 128 threads a block's rows are half a tile,
+    and the grid-stride loops over row blocks and chunks run many times.  Both geometries: the same bits.
+    Times on the CPU machine: 9 s a run and 8 s once for the reference, against 28 s for the file's slowest case."""
+    n = 16385
+    assert R.slice_tiles(n) == 3 and R.slices(n) == 22 and n % R.TJ == 1
+    csr, y, vel, gains, ref1 = large_inputs(n, 10.0)
+    ref = R.at_exaggeration(ref1, 12.0)
+    vel = settle(ref, y, vel, 12.0)
+    got = descend(exe, tmp_path, csr, y, vel, gains, 1, 12.0, 50.0, 0.5, grid=grid, threads=threads)
+    check_step(got, ref, y, vel, gains, 12.0, 50.0, 0.5)
+    key = tuple(got[name].tobytes() for name in ("y", "velocity", "gains", "grad")) + (got["kl"], got["z"])
+    assert _LARGE.setdefault("bits", key) == key
 
 
 def test_iterations_resume_and_evaluate(exe, tmp_path):
