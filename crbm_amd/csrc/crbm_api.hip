@@ -341,23 +341,19 @@ int big_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int 
   a.letters = d_letters;
   a.n = n; a.L = L; a.Lh = L - h->M + 1; a.LW = lw(h, L);
   const int pool = h->ms().POOL;
-  int ks = pool > 1 ? 8 : 32;                                // motifs per staged slab: a divisor of 32 whose filters fit 96 KB
-  while (ks > 1 && (size_t)big_hgv_ksp(ks) * h->M * h->A * 4 > 96 * 1024) ks >>= 1;   // (pooled: at most 8, the capacity of big_hgv_pooled_kernel)
-  a.KS = ks;
+  const BigHgvGeom g = big_hgv_geom(h->A, h->M, pool, n, L, a.LW, h->NW, h->num_cu);     // (crbm_plan.h)
+  a.KS = g.KS;
   a.pool = pool;
-  // rows per tile: enough tiles to cover the chip a few times over (every tile stages the filters once per slab), at most
-  // what the LDS takes of packed letters and ~4096 positions
-  a.TS = std::max(1, std::min(std::min((n + 4 * h->num_cu - 1) / (4 * h->num_cu), (32 * 1024) / (a.LW * 4)), std::max(1, 4096 / a.Lh)));
+  a.TS = g.TS;
   a.mode = mode;
   a.act = act; a.prob = prob; a.sample = sample; a.ones = ones; a.masks = masks;
   a.rng = rng_view(h, step, seq_offset);
   a.kind = kind;
-  const size_t lds = ((size_t)big_hgv_ksp(ks) * h->M * h->A + 32) * 4 + (size_t)a.TS * a.LW * 4;
-  ARGCHK(lds <= 160 * 1024, "motif_length too large for the h|v kernel");
+  const size_t lds = g.lds;
+  // (the filters of a slab take at most 96 KB: what exceeds the LDS is a row of letters beside them)
+  ARGCHK(lds <= BIG_LDS_MAX, "sequence too long for the h|v kernel of a model of this size");
   const int ntiles = (n + a.TS - 1) / a.TS;
-  // few tiles (small batches): one block per (tile, mask word) -- every slab lies inside one mask word, so blocks of
-  // different words never touch the same output
-  a.split = (h->NW > 1 && ntiles < 4 * h->num_cu) ? 1 : 0;
+  a.split = g.split;
   const dim3 grid(std::max(1, std::min(ntiles, h->num_cu * 8)), a.split ? h->NW : 1);
   if (pool > 1) hipLaunchKernelGGL(big_hgv_pooled_kernel, grid, dim3(256), lds, st, a);
   else hipLaunchKernelGGL(big_hgv_kernel, grid, dim3(256), lds, st, a);
@@ -371,10 +367,9 @@ int big_launch_gibbs(crbm_handle* h, int steps, hipStream_t st) {
   v.m = big_model(h);
   v.hm = h->d_hm; v.hmp = h->ds ? h->d_hmp : nullptr; v.vout = h->d_vf;
   v.nchains = h->B; v.Lf = h->Lf; v.Lv = h->Lv; v.LWs = h->LWs;
-  v.JS = std::max(1, std::min(h->M, (64 * 1024) / (32 * 4 * h->A)));
-  // DNA: activations in registers; any other alphabet: one position per thread, activations in LDS (big_vgh_any_kernel)
-  const size_t lds = h->A == 4 ? (size_t)v.JS * 32 * 16 + (size_t)BIG_VR * 256 + (size_t)2 * (std::min(BIG_VR * 256, h->Lv) + h->M - 1) * 4   // (+ one mask word of both strands for a chunk)
-                               : ((size_t)v.JS * 32 * h->A + (size_t)h->A * 256) * 4 + 256;
+  const BigVghGeom g = big_vgh_geom(h->A, h->M, h->Lv);      // (crbm_plan.h)
+  v.JS = g.JS;
+  const size_t lds = g.lds;
   HIPCHK(hipMemsetAsync(h->d_ones, 0, sizeof(unsigned long long), st));
   for (int t = 0; t < steps; ++t) {
     v.rng = rng_view(h, h->gibbs_step + (uint32_t)t, h->chain_offset);
@@ -421,19 +416,18 @@ int big_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bo
   a.letters = d_letters;
   a.n = n; a.L = L; a.Lh = L - M + 1; a.LW = lw(h, L);
   a.want_sparsity = data_half ? 1 : 0;
-  a.R = std::max(1, std::min(n, std::max(1, (h->num_cu * 8) / K)));
   a.pool = h->ms().POOL;
-  a.CH = std::max(64, std::min(4096, a.Lh));
-  a.CH = std::max(a.pool, a.CH - a.CH % a.pool);            // chunks start on pooling-group boundaries
+  const BigStatsGeom g = big_stats_geom(h->A, M, K, n, a.Lh, a.pool, h->num_cu);      // (crbm_plan.h)
+  a.R = g.R;
+  a.CH = g.CH;
   a.row = 3 * KAM + 3 * K + h->A;
   a.off_vh0 = 0; a.off_vh1 = KAM; a.off_h0 = 2 * KAM; a.off_h1 = 2 * KAM + K;
   a.off_sw = 2 * KAM + 2 * K; a.off_sb = 3 * KAM + 2 * K; a.off_v = 3 * KAM + 3 * K;
   HIPCHK(pbuf.ensure((size_t)a.R * a.row));
   a.partials = pbuf.p;
   ARGCHK(h->A * M <= BIG_ST * 256, "motif_length too large for the statistics kernel");
-  const size_t lds = (((size_t)h->A * M + 3) & ~(size_t)3) * 4 + (size_t)(a.pool > 1 ? 5 : 3) * a.CH * 4 + 64 + 12 * 256 * 4 +
-                     (size_t)((h->A + 3) & ~3) * 4 + (size_t)a.CH + M;
-  ARGCHK(lds <= 160 * 1024, "motif_length too large for the statistics kernel");
+  const size_t lds = g.lds;
+  ARGCHK(lds <= BIG_LDS_MAX, "motif_length too large for the statistics kernel");
   hipLaunchKernelGGL(big_stats_kernel, dim3(K, a.R), dim3(256), lds, st, a);
   HIPCHK(hipGetLastError());
   *reduce = reduce_args(h, data_half, pbuf.p, a.R, a.row, n);
@@ -453,8 +447,8 @@ int big_launch_eval(crbm_handle* h, const uint32_t* rows, int n, int L, int hits
   a.letters = rows;
   a.n = n; a.L = L; a.Lh = L - h->M + 1; a.LW = lw(h, L);
   a.fe = fe; a.fem = fem; a.hmax = hmax; a.hmean = hmean; a.pos_fx = pos_fx; a.hits = hits; a.pool = h->ms().POOL;
-  const size_t lds = (((size_t)h->A * h->M + 3) & ~(size_t)3) * 4 + 64 + (size_t)L;
-  ARGCHK(lds <= 160 * 1024, "sequence too long for the evaluation kernel of a model of this size");
+  const size_t lds = big_eval_lds(h->A, h->M, L);             // (crbm_plan.h)
+  ARGCHK(lds <= BIG_LDS_MAX, "sequence too long for the evaluation kernel of a model of this size");
   hipLaunchKernelGGL(big_eval_kernel, dim3(std::max(1, std::min(n, h->num_cu * 8))), dim3(256), lds, st, a);
   HIPCHK(hipGetLastError());
   return CRBM_OK;
@@ -2319,12 +2313,13 @@ int crbm_v_given_h(crbm_handle* h, const float* hid, const float* hid_prime, int
   a.kind = KIND_API_V;
   const int ntiles = (n + a.TS - 1) / a.TS;
   if (h->A == 4) {
+    // (the filters pass through LDS a slab of motifs at a time: vgh_dense_ks, crbm_layout.h -- any accepted model fits)
     hipLaunchKernelGGL(vgh_dense_kernel, dim3(std::max(1, std::min(ntiles, h->num_cu * 8))), dim3(256),
-                       (size_t)h->M * h->K * 16, h->stream, a);
+                       vgh_dense_lds(4, h->K, h->M), h->stream, a);
   } else {      // any other alphabet: a position's activations of all letters in LDS, filters from global memory
     VghAnyArgs aa;
     aa.g = a; aa.A = h->A;
-    hipLaunchKernelGGL(vgh_dense_any_kernel, dim3(grid_for((long)n * L, 256, h->num_cu * 8)), dim3(256), (size_t)h->A * 256 * 4, h->stream, aa);
+    hipLaunchKernelGGL(vgh_dense_any_kernel, dim3(grid_for((long)n * L, 256, h->num_cu * 8)), dim3(256), vgh_dense_lds(h->A, h->K, h->M), h->stream, aa);
   }
   HIPCHK(hipGetLastError());
   int rc;

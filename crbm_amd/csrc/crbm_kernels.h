@@ -4121,42 +4121,65 @@ struct VghArgs {
   uint32_t kind;
 };
 
+// The filters pass through LDS a slab of KS motifs at a time (vgh_dense_ks, crbm_layout.h: a fixed budget, so every model
+// the constructor accepts can be launched); a position's four activations stay in registers across the slabs, and the
+// additions keep their order -- motif outer, column inner -- whatever the slab size.  A model of one slab stages its
+// filters once per block; a larger one stages every slab once per round of blockDim positions (an API / test pass).
 __global__ void __launch_bounds__(256) vgh_dense_kernel(VghArgs a) {
   HIP_DYNAMIC_SHARED(float, smem);
-  const int K = a.K, M = a.M;
-  float4* W4 = reinterpret_cast<float4*>(smem);   // [j][k] -> W[k][0..3][j]
-  for (int idx = threadIdx.x; idx < M * K; idx += blockDim.x) {
-    const int j = idx / K, k = idx - j * K;
-    W4[idx] = make_float4(a.W[(k * 4 + 0) * M + j], a.W[(k * 4 + 1) * M + j],
-                          a.W[(k * 4 + 2) * M + j], a.W[(k * 4 + 3) * M + j]);
+  const int K = a.K, M = a.M, KS = vgh_dense_ks(K, M);
+  const bool one_slab = KS >= K;
+  float4* W4 = reinterpret_cast<float4*>(smem);   // [j][k - k0] -> W[k][0..3][j] of the slab's motifs
+  auto stage = [&](int k0, int kc) {
+    for (int idx = threadIdx.x; idx < M * kc; idx += blockDim.x) {
+      const int j = idx / kc, k = k0 + idx - j * kc;
+      W4[idx] = make_float4(a.W[(k * 4 + 0) * M + j], a.W[(k * 4 + 1) * M + j],
+                            a.W[(k * 4 + 2) * M + j], a.W[(k * 4 + 3) * M + j]);
+    }
+  };
+  if (one_slab) {
+    stage(0, K);
+    __syncthreads();
   }
-  __syncthreads();
   const float c0 = a.c[0], c1 = a.c[1], c2 = a.c[2], c3 = a.c[3];
   const int ntiles = (a.n + a.TS - 1) / a.TS;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int n0 = tile * a.TS;
     const int ns = min(a.TS, a.n - n0);
     const uint32_t items = (uint32_t)ns * (uint32_t)a.L;
-    for (uint32_t i = threadIdx.x; i < items; i += blockDim.x) {
-      const uint32_t nl = fastdiv(i, a.divL);
+    // (a round of blockDim positions: the bound is the block's, so every thread meets the barriers of the slab loop)
+    for (uint32_t i0 = 0; i0 < items; i0 += blockDim.x) {
+      const uint32_t i = i0 + threadIdx.x;
+      const bool live = i < items;
+      const uint32_t nl = live ? fastdiv(i, a.divL) : 0u;
       const int p = (int)(i - nl * (uint32_t)a.L);
       const int nn = n0 + (int)nl;
       float y0 = c0, y1 = c1, y2 = c2, y3 = c3;
       const int jlo = max(0, p - a.Lh + 1), jhi = min(M - 1, p);
-      for (int k = 0; k < K; ++k) {
-        const float* hrow = a.hid + ((size_t)nn * K + k) * a.Lh;
-        const float* hprow = a.hidp ? a.hidp + ((size_t)nn * K + k) * a.Lh : nullptr;
-        for (int j = jlo; j <= jhi; ++j) {
-          const float hv = hrow[p - j];
-          const float4 w = W4[j * K + k];
-          y0 = fmaf(w.x, hv, y0); y1 = fmaf(w.y, hv, y1); y2 = fmaf(w.z, hv, y2); y3 = fmaf(w.w, hv, y3);
-          if (hprow) {   // rc(W)[k,a,j] = W[k,3-a,M-1-j]
-            const float hp = hprow[p - j];
-            const float4 wr = W4[(M - 1 - j) * K + k];
-            y0 = fmaf(wr.w, hp, y0); y1 = fmaf(wr.z, hp, y1); y2 = fmaf(wr.y, hp, y2); y3 = fmaf(wr.x, hp, y3);
+      for (int k0 = 0; k0 < K; k0 += KS) {
+        const int kc = min(KS, K - k0);
+        if (!one_slab) {
+          __syncthreads();                        // the previous slab is still being read
+          stage(k0, kc);
+          __syncthreads();
+        }
+        if (!live) continue;
+        for (int k = k0; k < k0 + kc; ++k) {
+          const float* hrow = a.hid + ((size_t)nn * K + k) * a.Lh;
+          const float* hprow = a.hidp ? a.hidp + ((size_t)nn * K + k) * a.Lh : nullptr;
+          for (int j = jlo; j <= jhi; ++j) {
+            const float hv = hrow[p - j];
+            const float4 w = W4[j * kc + (k - k0)];
+            y0 = fmaf(w.x, hv, y0); y1 = fmaf(w.y, hv, y1); y2 = fmaf(w.z, hv, y2); y3 = fmaf(w.w, hv, y3);
+            if (hprow) {   // rc(W)[k,a,j] = W[k,3-a,M-1-j]
+              const float hp = hprow[p - j];
+              const float4 wr = W4[(M - 1 - j) * kc + (k - k0)];
+              y0 = fmaf(wr.w, hp, y0); y1 = fmaf(wr.z, hp, y1); y2 = fmaf(wr.y, hp, y2); y3 = fmaf(wr.x, hp, y3);
+            }
           }
         }
       }
+      if (!live) continue;
       const size_t o = (size_t)nn * 4 * a.L + p;
       if (a.act) { a.act[o] = y0; a.act[o + a.L] = y1; a.act[o + 2 * a.L] = y2; a.act[o + 3 * a.L] = y3; }
       const float mx = fmaxf(fmaxf(y0, y1), fmaxf(y2, y3));

@@ -66,8 +66,7 @@ struct BigHgvArgs {
   uint32_t kind;
 };
 
-// floats per (column, letter) row of a slab of KS motifs in LDS
-__host__ __device__ inline int big_hgv_ksp(int KS) { return ((KS + 3) & ~3) + 4; }
+// (big_hgv_ksp, crbm_layout.h: floats per (column, letter) row of a slab of KS motifs in LDS)
 // KSM: slab capacity of the register arrays (32 unpooled; 8 pooled, which keeps five arrays per unit).
 // POOLED: the units of `pool` consecutive positions compete (convRBM.py:245-267): P_i = exp(x_i) / (pool + sum_j exp(x_j)),
 // one draw per group -- the uniform of its first position -- against the cumulative probabilities; a thread evaluates its
@@ -221,8 +220,8 @@ __global__ void __launch_bounds__(256) big_hgv_pooled_kernel(BigHgvArgs a) { big
 
 // ---- v | h of the chain from the masks (convRBM.py:277-325): y[a,p] = c[a] + sum_k sum_j W[k,a,j] h[k,p-j] (+ rc strand),
 // softmax over the four letters, one categorical draw per position.  One block per chain; a thread owns up to BIG_VR
-// positions and keeps their activations in registers while the filters pass through LDS 32 motifs x JS columns at a time.
-constexpr int BIG_VR = 8;
+// positions (crbm_layout.h) and keeps their activations in registers while the filters pass through LDS 32 motifs x JS
+// columns at a time.
 struct BigVghArgs {
   BigModel m;
   const uint32_t* hm;       // [nchains][Lf][NW]
@@ -396,7 +395,7 @@ __global__ void __launch_bounds__(256) big_vgh_any_kernel(BigVghArgs a) {
 // ---- gradient statistics (convRBM.py:327-371) and the sparsity sums (:440-451), raw sums into partial rows of the layout
 // the column reduction expects.  Block (k, r): motif k, rows r, r + R, ...; the motif's filter, a chunk of letters and
 // the probabilities of the chunk's positions sit in LDS; thread t accumulates VH[k, a, j] for (a, j) = t / M, t % M.
-constexpr int BIG_ST = 8;                                   // (a, j) slots per thread: A M <= BIG_ST * blockDim
+// (BIG_ST, crbm_layout.h: (a, j) slots per thread, A M <= BIG_ST * blockDim)
 struct BigStatsArgs {
   BigModel m;
   const uint32_t* letters;

@@ -42,6 +42,20 @@ inline int letter_words(int L) { return (L + 15) / 16 + 2; }
 // Alphabets of A != 4 letters (input_dims, convRBM.py:68; generic kernels only): one byte per letter, four per word,
 // the same two pad words.
 inline int letter_words_any(int A, int L) { return A == 4 ? letter_words(L) : (L + 3) / 4 + 2; }
+// The generic kernels (crbm_kernels_generic.h) and the host's geometry for them (crbm_plan.h) share these capacities:
+// positions per thread of the DNA chain v|h kernel, (letter, column) slots per thread of the statistics kernel, and the
+// floats per (column, letter) row of an h|v slab of KS motifs in LDS.
+constexpr int BIG_VR = 8;
+constexpr int BIG_ST = 8;                                   // (a, j) slots per thread: A M <= BIG_ST * blockDim
+constexpr int big_hgv_ksp(int KS) { return ((KS + 3) & ~3) + 4; }
+// Dense v|h of DNA models (crbm_kernels.h, vgh_dense_kernel): the filters pass through LDS a slab of motifs at a time, as
+// float4 per (column, motif), within this budget -- every model the constructor accepts has a slab of at least 8 motifs
+// (motif_length <= 512), a model of up to 4096 filter columns is one slab, staged once per block.
+constexpr int VGH_DENSE_LDS = 64 * 1024;
+constexpr int vgh_dense_ks(int K, int M) {
+  const int cap = VGH_DENSE_LDS / (M * 16);
+  return K < cap ? K : (cap < 1 ? 1 : cap);
+}
 // Mutagenesis kernel (crbm_kernels.h, mutagenesis_body): floats per plane of a wave's LDS accumulator, three planes per wave
 constexpr int mut_plane(int L) { return (L + 63) & ~63; }
 // Stream scan (crbm_kernels.h, scan_sites_body): a segment of n letters lives on the device as a validity plane, one

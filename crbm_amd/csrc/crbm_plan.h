@@ -147,6 +147,65 @@ inline bool model_needs_big(const ModelShape& ms, int Lf, int B, int num_cu) {
   return false;
 }
 
+// ---- geometry of the generic ("big") kernels (crbm_kernels_generic.h), all launched with 256-thread blocks -----------------
+// The one place the host derives it: crbm_api.hip launches by these, tests/test_generic_geom_host.py reads them on the CPU
+// (tests/emu/plan_driver.cpp) and holds every GPU case of tests/test_gpu_generic_geometry.py to the regime it is named for.
+constexpr int BIG_THREADS = 256;
+constexpr size_t BIG_LDS_MAX = 160 * 1024;
+
+// h | v (big_hgv_kernel, big_hgv_pooled_kernel) of n rows of L letters in LW words, masks of NW words
+struct BigHgvGeom { int KS, TS, split; size_t lds; };
+inline BigHgvGeom big_hgv_geom(int A, int M, int pool, int n, int L, int LW, int NW, int num_cu) {
+  BigHgvGeom g;
+  const int Lh = L - M + 1;
+  int ks = pool > 1 ? 8 : 32;                                // motifs per staged slab: a divisor of 32 whose filters fit 96 KB
+  while (ks > 1 && (size_t)big_hgv_ksp(ks) * M * A * 4 > 96 * 1024) ks >>= 1;   // (pooled: at most 8, the capacity of big_hgv_pooled_kernel)
+  g.KS = ks;
+  // rows per tile: enough tiles to cover the chip a few times over (every tile stages the filters once per slab), at most
+  // what the LDS takes of packed letters and ~4096 positions
+  g.TS = std::max(1, std::min(std::min((n + 4 * num_cu - 1) / (4 * num_cu), (32 * 1024) / (LW * 4)), std::max(1, 4096 / Lh)));
+  g.lds = ((size_t)big_hgv_ksp(ks) * M * A + 32) * 4 + (size_t)g.TS * LW * 4;
+  const int ntiles = (n + g.TS - 1) / g.TS;
+  // few tiles (small batches): one block per (tile, mask word) -- every slab lies inside one mask word, so blocks of
+  // different words never touch the same output
+  g.split = (NW > 1 && ntiles < 4 * num_cu) ? 1 : 0;
+  return g;
+}
+
+// v | h of the chain (big_vgh_kernel for DNA, big_vgh_any_kernel): filter columns per staged slab, positions per chunk
+struct BigVghGeom { int JS, CH; size_t lds; };
+// (threads, JS: the CPU program tests/emu/big_vgh_main.cpp runs the kernels with 64-thread blocks and narrower slabs)
+inline BigVghGeom big_vgh_geom(int A, int M, int Lv, int threads = BIG_THREADS, int JS = 0) {
+  BigVghGeom g;
+  g.JS = JS > 0 ? JS : std::max(1, std::min(M, (64 * 1024) / (32 * 4 * A)));
+  g.CH = A == 4 ? BIG_VR * threads : threads;
+  // DNA: activations in registers; any other alphabet: one position per thread, activations in LDS (big_vgh_any_kernel)
+  g.lds = A == 4 ? (size_t)g.JS * 32 * 16 + (size_t)g.CH + (size_t)2 * (std::min(g.CH, Lv) + M - 1) * 4   // (+ one mask word of both strands for a chunk)
+                 : ((size_t)g.JS * 32 * A + (size_t)A * threads) * 4 + threads;
+  return g;
+}
+
+// statistics (big_stats_kernel, grid K x R): rows a block strides by, hidden positions per chunk
+struct BigStatsGeom { int R, CH; size_t lds; };
+inline BigStatsGeom big_stats_geom(int A, int M, int K, int n, int Lh, int pool, int num_cu) {
+  BigStatsGeom g;
+  g.R = std::max(1, std::min(n, std::max(1, (num_cu * 8) / K)));
+  g.CH = std::max(64, std::min(4096, Lh));
+  g.CH = std::max(pool, g.CH - g.CH % pool);                // chunks start on pooling-group boundaries
+  g.lds = (((size_t)A * M + 3) & ~(size_t)3) * 4 + (size_t)(pool > 1 ? 5 : 3) * g.CH * 4 + 64 + 12 * BIG_THREADS * 4 +
+          (size_t)((A + 3) & ~3) * 4 + (size_t)g.CH + M;
+  return g;
+}
+
+// free energies and hit summaries (big_eval_kernel): the filter of one motif and the letters of a row as bytes
+inline size_t big_eval_lds(int A, int M, int L) { return (((size_t)A * M + 3) & ~(size_t)3) * 4 + 64 + (size_t)L; }
+
+// dense v | h (crbm_v_given_h): DNA stages a slab of motifs (vgh_dense_kernel), any other alphabet keeps a position's
+// activations of all letters in LDS (vgh_dense_any_kernel)
+inline size_t vgh_dense_lds(int A, int K, int M) {
+  return A == 4 ? (size_t)vgh_dense_ks(K, M) * M * 16 : (size_t)A * BIG_THREADS * 4;
+}
+
 // block-size bound the chain kernels are compiled with
 inline int gibbs_block_bound(int threads) { return threads > 512 ? 1024 : threads > 256 ? 512 : 256; }
 

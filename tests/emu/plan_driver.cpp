@@ -8,6 +8,10 @@
 //                     GPU: it must follow them (tests/test_gpu_sweeps.py, test_launch_info_is_the_recorded_plan, checks the
 //                     real function against the same fixture); the geometry itself comes from the shared plain_geom.
 //   plan_block_bound: gibbs_block_bound.
+//   big_geom_ints:    the geometry of the generic kernels for tests/test_generic_geom_host.py, BIG_GEOM_INTS ints: h|v (KS, TS,
+//                     split, lds) of n rows of L letters, chain v|h (JS, CH, lds) of chains of Lf hidden positions, statistics
+//                     (R, CH, lds) of the n rows, the LDS of the evaluation kernel and of the dense v|h pass (slab of
+//                     vgh_dense_ks motifs), and LW, NW.
 #include "crbm_plan.h"
 
 #include <cstring>
@@ -48,3 +52,15 @@ extern "C" void plan_launch_info(int K, int M, int ds, int A, int pool, int Lf, 
 }
 
 extern "C" int plan_block_bound(int threads) { return gibbs_block_bound(threads); }
+
+extern "C" int big_geom_ints(int K, int M, int A, int pool, int n, int L, int Lf, int num_cu, long* out) {
+  const int LW = letter_words_any(A, L), NW = (K + 31) / 32, Lh = L - M + 1;
+  const BigHgvGeom h = big_hgv_geom(A, M, pool, n, L, LW, NW, num_cu);
+  const BigVghGeom v = big_vgh_geom(A, M, Lf + M - 1);
+  const BigStatsGeom s = big_stats_geom(A, M, K, n, Lh, pool, num_cu);
+  int i = 0;
+  for (long x : {(long)h.KS, (long)h.TS, (long)h.split, (long)h.lds, (long)v.JS, (long)v.CH, (long)v.lds, (long)s.R, (long)s.CH, (long)s.lds,
+                 (long)big_eval_lds(A, M, L), (long)vgh_dense_lds(A, K, M), (long)(A == 4 ? vgh_dense_ks(K, M) : K), (long)LW, (long)NW})
+    out[i++] = x;
+  return i;
+}
