@@ -13,5 +13,7 @@ from .calibrate import ScoreHistogram  # noqa: F401
 from .utils import saveMotifs, saveSites, runTSNE  # noqa: F401
 from .tsne import tsneEmbed, symmetrize  # noqa: F401
 from . import tsne  # noqa: F401
+from .background import MarkovBackground, fitBackground, sampleBackground  # noqa: F401
+from . import background  # noqa: F401
 
 __version__ = "0.1.0"

@@ -584,7 +584,8 @@ class CRBM(object):
     def scoreHistogram(self, stream, bins=512, lo=-16.0, hi=16.0, offsets=None):
         """The scores scanSites would see on `stream`, as a calibrate.ScoreHistogram: per motif and strand the counts of
         the log-odds x (prob = sigmoid(x)) of every valid window in `bins` equal bins over [lo, hi), the first and the
-        last bin open to the outside.  Run it on a background -- sequences.shuffleStream(stream, seed) of the data --
+        last bin open to the outside.  Run it on a background -- sequences.shuffleStream(stream, seed) of the data, or
+        background.sampleBackground from a Markov background fitted to it, which keeps the dinucleotide dependence --
         and take per-motif thresholds (thresholds(fpr)) or p-values of scanSites records (pvalues(sites)) from the
         result.  Nothing but the counts leaves the device.  `stream` and `offsets` as in scanSites; lo and hi are
         rounded to float32.  The same models are refused, and more than 1024 bins."""

@@ -7,6 +7,7 @@
 #include "crbm_plan.h"
 #include "crbm_sweep.h"
 #include "crbm_tsne.h"
+#include "crbm_background.h"
 #include "../../include/crbm_amd.h"
 
 #include <dlfcn.h>
@@ -245,6 +246,7 @@ struct crbm_handle {
   bool slab_hgv = false;               // the chain's h|v takes the slabs too (slab a multiple of ten motifs, or one slab: sampler groups)
   uint64_t slab_tables_version = 0;
   float tsne_ms = 0.f;                 // device time of the iterations of the last crbm_tsne_descend call (HIP events)
+  float bg_ms = 0.f;                   // device time of the kernels of the last crbm_stream_kmer_counts / crbm_background_sample call
   std::string slab_note;               // why the slabs are off, if they are (crbm_launch_info prints nothing of it; a debugging aid)
   std::string err;
 };
@@ -3871,6 +3873,187 @@ int crbm_tsne_descend(crbm_handle* h, int64_t n, const int64_t* indptr, const in
 int crbm_tsne_descend_ms(crbm_handle* h, float* ms) {
   if (!h || !ms) return CRBM_ERR_INVALID;
   *ms = h->tsne_ms;
+  return CRBM_OK;
+}
+
+}  // extern "C"
+
+// ---- Markov backgrounds (crbm_background.h): the handle lends its device, its two streams and its error string; the
+// model plays no part (StreamSweep::admit refuses by model and is not used) ---------------------------------------------
+namespace {
+
+// events of one call, destroyed whichever way the call ends
+struct BgEvents {
+  hipEvent_t walk[2] = {nullptr, nullptr};             // a set's walk kernel has left the carry of the next segment
+  hipEvent_t t[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // around a set's kernels
+  ~BgEvents() {
+    for (hipEvent_t e : walk)
+      if (e) (void)hipEventDestroy(e);
+    for (auto& set : t)
+      for (hipEvent_t e : set)
+        if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t create() {
+    for (auto& e : walk) {
+      const hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+      if (rc != hipSuccess) return rc;
+    }
+    for (auto& set : t)
+      for (auto& e : set) {
+        const hipError_t rc = hipEventCreate(&e);
+        if (rc != hipSuccess) return rc;
+      }
+    return hipSuccess;
+  }
+};
+
+// positions per segment: the slab budget (CRBM_SLAB_BYTES) at `bytes_per_position`, within 32 MB unless set by hand
+int bg_segment(int64_t T, size_t bytes_per_position) {
+  const SlabBudget budget = slab_budget();
+  size_t seg = std::max<size_t>(budget.bytes / bytes_per_position, 1);
+  if (!budget.was_set) seg = std::min(seg, std::max<size_t>(1, (32u << 20) / bytes_per_position));
+  return (int)std::min<size_t>(seg, (size_t)std::max<int64_t>(T, 1));
+}
+
+void bg_drain(crbm_handle* h) {
+  (void)hipStreamSynchronize(h->stream2);
+  (void)hipStreamSynchronize(h->stream);
+}
+
+template <int ORDER>
+int bg_sample_launch(crbm_handle* h, const bg::SampleArgs& a, hipStream_t st, hipEvent_t wait_for, hipEvent_t walked) {
+  constexpr int NS = bg::contexts(ORDER);
+  const unsigned lanes_grid = (unsigned)grid_for((long)a.chunks, 64, h->num_cu * 32), group_grid = (unsigned)grid_for((long)a.groups, 64, h->num_cu * 32);
+  hipLaunchKernelGGL(bg::sample_maps_kernel<ORDER>, dim3(lanes_grid), dim3(64), NS * 16, st, a);
+  hipLaunchKernelGGL(bg::sample_groups_kernel<ORDER>, dim3(group_grid), dim3(64), 0, st, a);
+  if (wait_for) HIPCHK(hipStreamWaitEvent(st, wait_for, 0));          // the carry of the segment before
+  hipLaunchKernelGGL(bg::sample_walk_kernel<ORDER>, dim3(1), dim3(256), bg::WALK_TILE * NS, st, a);
+  HIPCHK(hipEventRecord(walked, st));
+  hipLaunchKernelGGL(bg::sample_entries_kernel<ORDER>, dim3(group_grid), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(bg::sample_letters_kernel<ORDER>, dim3(lanes_grid), dim3(64), NS * 16, st, a);
+  HIPCHK(hipGetLastError());
+  return CRBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crbm_stream_kmer_counts(crbm_handle* h, const uint8_t* codes, int64_t T, int32_t order, uint64_t* counts) {
+  ENTER();
+  if (const char* why = bg::counts_refusal(codes, T, order, counts)) return fail(h, CRBM_ERR_INVALID, std::string("crbm_stream_kmer_counts: ") + why);
+  const int slots = bg::kmer_slots(order), seg = bg_segment(T, 1), nsets = seg < T ? 2 : 1;
+  TsneScratch s;
+  unsigned long long* dcounts = nullptr;
+  uint8_t* dcodes[2] = {nullptr, nullptr};
+  HIPCHK(s.get(&dcounts, (size_t)slots));
+  for (int i = 0; i < nsets; ++i) HIPCHK(s.get(&dcodes[i], (size_t)seg + order));
+  BgEvents ev;
+  HIPCHK(ev.create());
+  HIPCHK(hipMemsetAsync(dcounts, 0, (size_t)slots * 8, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));               // (the second stream adds to the counters too)
+  double device_ms = 0.0;
+  const int rc = run_slabs((int)T, seg, 2,
+    [&](int, int si, int start, int cnt) -> int {
+      const hipStream_t st = si ? h->stream2 : h->stream;
+      const int64_t n = std::min<int64_t>((int64_t)cnt + order, T - start);   // the halo: `order` codes behind the segment's own
+      HIPCHK(hipMemcpyAsync(dcodes[si], codes + start, (size_t)n, hipMemcpyHostToDevice, st));
+      HIPCHK(hipEventRecord(ev.t[si][0], st));
+      const bg::KmerArgs a{dcodes[si], dcounts, n, cnt, order};
+      hipLaunchKernelGGL(bg::kmer_count_kernel, dim3(grid_for(cnt, 256, h->num_cu * 8)), dim3(256), (size_t)slots * 4, st, a);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(ev.t[si][1], st));
+      return CRBM_OK;
+    },
+    [&](int, int si, int, int) -> int {
+      HIPCHK(hipStreamSynchronize(si ? h->stream2 : h->stream));
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev.t[si][0], ev.t[si][1]));
+      device_ms += ms;
+      return CRBM_OK;
+    },
+    [&] { bg_drain(h); });
+  if (rc) return rc;
+  std::vector<unsigned long long> got((size_t)slots);
+  HIPCHK(hipMemcpyAsync(got.data(), dcounts, (size_t)slots * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int e = 0; e < slots; ++e) counts[e] = got[e];
+  h->bg_ms = (float)device_ms;
+  return CRBM_OK;
+}
+
+int crbm_background_sample(crbm_handle* h, const uint32_t* thr, int32_t order, int64_t T, int64_t pos0, uint64_t seed,
+                           const uint8_t* tmpl, uint8_t* out) {
+  ENTER();
+  if (const char* why = bg::sample_refusal(thr, order, T, pos0, tmpl, out)) return fail(h, CRBM_ERR_INVALID, std::string("crbm_background_sample: ") + why);
+  h->bg_ms = 0.f;
+  if (T == 0) return CRBM_OK;
+  const int NS = bg::contexts(order), chunk = bg::chunk_length(env_int("CRBM_BG_CHUNK", bg::CHUNK_DEFAULT));
+  const int seg = bg_segment(T, 3), nsets = seg < T ? 2 : 1;
+  const int64_t seg_chunks = ((int64_t)seg + chunk - 1) / chunk, seg_groups = (seg_chunks + bg::GROUP - 1) / bg::GROUP;
+  uint32_t rows[4 * bg::contexts(bg::MAX_ORDER)];
+  bg::build_rows(thr, order, rows);
+  TsneScratch s;
+  uint4* drows = nullptr;
+  uint8_t *dcarry = nullptr, *dtmpl[2] = {nullptr, nullptr}, *dout[2] = {nullptr, nullptr}, *dcmap[2] = {nullptr, nullptr},
+          *dgmap[2] = {nullptr, nullptr}, *dcentry[2] = {nullptr, nullptr}, *dgentry[2] = {nullptr, nullptr};
+  HIPCHK(s.get(&drows, (size_t)NS));
+  HIPCHK(s.get(&dcarry, 4));
+  for (int i = 0; i < nsets; ++i) {
+    if (tmpl) HIPCHK(s.get(&dtmpl[i], (size_t)seg));
+    HIPCHK(s.get(&dout[i], (size_t)seg));
+    HIPCHK(s.get(&dcmap[i], (size_t)seg_chunks * NS));
+    HIPCHK(s.get(&dgmap[i], (size_t)seg_groups * NS));
+    HIPCHK(s.get(&dcentry[i], (size_t)seg_chunks));
+    HIPCHK(s.get(&dgentry[i], (size_t)seg_groups));
+  }
+  BgEvents ev;
+  HIPCHK(ev.create());
+  HIPCHK(hipMemcpyAsync(drows, rows, (size_t)NS * 16, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(dcarry, 0, 4, h->stream));       // the empty context
+  HIPCHK(hipStreamSynchronize(h->stream));               // (the second stream reads both)
+  double device_ms = 0.0;
+  const int rc = run_slabs((int)T, seg, 2,
+    [&](int i, int si, int start, int cnt) -> int {
+      const hipStream_t st = si ? h->stream2 : h->stream;
+      if (tmpl) HIPCHK(hipMemcpyAsync(dtmpl[si], tmpl + start, (size_t)cnt, hipMemcpyHostToDevice, st));
+      HIPCHK(hipEventRecord(ev.t[si][0], st));
+      bg::SampleArgs a;
+      a.rows = drows; a.tmpl = tmpl ? dtmpl[si] : nullptr; a.out = dout[si];
+      a.cmap = dcmap[si]; a.gmap = dgmap[si]; a.centry = dcentry[si]; a.gentry = dgentry[si]; a.carry = dcarry;
+      a.n = cnt; a.pos0 = pos0 + start;
+      a.chunks = ((int64_t)cnt + chunk - 1) / chunk; a.groups = (a.chunks + bg::GROUP - 1) / bg::GROUP;
+      a.chunk = chunk; a.seed_lo = (uint32_t)(seed & 0xffffffffu); a.seed_hi = (uint32_t)(seed >> 32);
+      const hipEvent_t before = i > 0 ? ev.walk[si ^ 1] : nullptr;
+      int r = CRBM_OK;
+      switch (order) {
+        case 0: r = bg_sample_launch<0>(h, a, st, before, ev.walk[si]); break;
+        case 1: r = bg_sample_launch<1>(h, a, st, before, ev.walk[si]); break;
+        case 2: r = bg_sample_launch<2>(h, a, st, before, ev.walk[si]); break;
+        default: r = bg_sample_launch<3>(h, a, st, before, ev.walk[si]); break;
+      }
+      if (r) return r;
+      HIPCHK(hipEventRecord(ev.t[si][1], st));
+      return CRBM_OK;
+    },
+    [&](int, int si, int start, int cnt) -> int {
+      const hipStream_t st = si ? h->stream2 : h->stream;
+      HIPCHK(hipMemcpyAsync(out + start, dout[si], (size_t)cnt, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev.t[si][0], ev.t[si][1]));
+      device_ms += ms;
+      return CRBM_OK;
+    },
+    [&] { bg_drain(h); });
+  if (rc) return rc;
+  h->bg_ms = (float)device_ms;
+  return CRBM_OK;
+}
+
+int crbm_background_ms(crbm_handle* h, float* ms) {
+  if (!h || !ms) return CRBM_ERR_INVALID;
+  *ms = h->bg_ms;
   return CRBM_OK;
 }
 

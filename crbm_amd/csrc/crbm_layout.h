@@ -10,7 +10,8 @@ namespace crbm {
 // oracle/crbm_oracle.py.
 enum : uint32_t {
   KIND_CHAIN_H = 1, KIND_CHAIN_V = 2, KIND_EVAL_H = 3, KIND_API_H = 4, KIND_API_V = 5,
-  KIND_AIS_H = 6, KIND_AIS_V = 7      // annealed importance sampling (crbm_ais), keyed by the seed of the call
+  KIND_AIS_H = 6, KIND_AIS_V = 7,     // annealed importance sampling (crbm_ais), keyed by the seed of the call
+  KIND_BACKGROUND = 8                 // Markov background letters (crbm_background_sample), keyed by the seed of the call
 };
 
 // n / d via one mul_hi (d >= 1).  With inv = floor(2^32 / d) + 1 the estimate

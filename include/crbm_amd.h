@@ -517,6 +517,44 @@ int crbm_tsne_descend(crbm_handle* h, int64_t n, const int64_t* indptr, const in
                       float* grad_last, double* kl, double* z);
 int crbm_tsne_descend_ms(crbm_handle* h, float* ms);
 
+/* ---- Markov backgrounds: j-mer counts of a stream and exact sampling (the --bgfile of motif scanners) ------------
+ * Model-independent: the handle of any model lends its device, its two streams and its error string.  Every pointer is
+ * host memory; every call is complete when it returns.  Integer arithmetic only: the same inputs give the same bits in
+ * every run, whatever the launch geometry, the segment size (CRBM_SLAB_BYTES) or the chunk length (CRBM_BG_CHUNK).
+ * (Additive: the ABI version stays.)
+ *
+ * Codes are those of crbm_scan_sites_codes: 0..3 = A, C, G, T; 4 = no letter (a gap: N, a record separator).
+ * A context is the last j <= order letters l_1 .. l_j, oldest first, with the index
+ *   (4^j - 1) / 3 + sum_i l_i 4^(j - i);   0 is the empty context.
+ * An order has (4^(order + 1) - 1) / 3 = 1, 5, 21, 85 contexts.
+ *
+ * crbm_stream_kmer_counts: for every j = 1 .. order + 1 and every j-mer, the number of positions p of the stream at
+ * which all of codes[p .. p + j) are letters and spell it.  counts holds sum_j 4^j = 4, 20, 84, 340 entries: the 1-mers,
+ * then the 2-mers, ..., each block indexed with the oldest letter most significant.  Long streams go to the device in
+ * segments with a halo of `order` codes, on two buffer sets.
+ * CRBM_ERR_INVALID: order outside [0, 3], T < 0 or T > 2^31 - 1, a null pointer (codes may be null when T == 0), a code
+ * above 4.  counts is not written then, and the handle stays usable.
+ *
+ * crbm_background_sample: T codes of a Markov chain of the given order.  thr is the threshold table, (contexts, 3)
+ * uint32, every row ascending: thr[ctx][i] = min(2^32 - 1, floor(2^32 sum_{a <= i} P(a | ctx))).  With P = pos0 + p:
+ *   draw    u_p = word (P & 3) of philox4x32(c0 = (uint32)(P >> 2), c1 = (uint32)(P >> 34), c2 = 8 << 28, c3 = 0,
+ *           key = (seed & 0xffffffff, seed >> 32)), seven rounds (8 is KIND_BACKGROUND of crbm_layout.h);
+ *   gap     where tmpl holds a 4, out holds a 4 and the context becomes empty;
+ *   letter  otherwise out[p] = a = #{ i < 3 : u_p >= thr[ctx][i] }, and the context becomes its last `order` letters
+ *           with a appended (fewer while fewer have been drawn since the start or the last gap).
+ * The context is empty at p = 0.  tmpl may be null: all letters.  A stream longer than one call takes is cut behind a
+ * gap and every piece called with its pos0: the pieces are the stream of one call.  Exact: the chain is never
+ * restarted from anything but its true context (composed transition maps, crbm_background.h).
+ * CRBM_ERR_INVALID: order outside [0, 3], T < 0 or T > 2^31 - 1, pos0 < 0 or pos0 > 2^62, a null thr or out, a row of
+ * thr that does not ascend, a code above 4 in tmpl.  out is not written then, and the handle stays usable.
+ *
+ * crbm_background_ms: device time (HIP events around the kernels of every segment, summed) of the handle's last
+ * crbm_stream_kmer_counts or crbm_background_sample call. */
+int crbm_stream_kmer_counts(crbm_handle* h, const uint8_t* codes, int64_t T, int32_t order, uint64_t* counts);
+int crbm_background_sample(crbm_handle* h, const uint32_t* thr, int32_t order, int64_t T, int64_t pos0,
+                           uint64_t seed, const uint8_t* tmpl, uint8_t* out);
+int crbm_background_ms(crbm_handle* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
