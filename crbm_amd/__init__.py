@@ -15,5 +15,7 @@ from .tsne import tsneEmbed, symmetrize  # noqa: F401
 from . import tsne  # noqa: F401
 from .background import MarkovBackground, fitBackground, sampleBackground  # noqa: F401
 from . import background  # noqa: F401
+from .null import ScoreDistribution, scoreDistribution  # noqa: F401
+from . import null  # noqa: F401
 
 __version__ = "0.1.0"

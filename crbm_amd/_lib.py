@@ -152,6 +152,9 @@ SIGNATURES = {
     "crbm_stream_kmer_counts": (_I32, [_H, _U8P, _I64, _I32, ctypes.POINTER(_U64)]),
     "crbm_background_sample": (_I32, [_H, ctypes.POINTER(_U32), _I32, _I64, _I64, _U64, _U8P, _U8P]),
     "crbm_background_ms": (_I32, [_H, _F]),
+    "crbm_score_distribution": (_I32, [_H, _I32P, _I32, _I32, _I32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _I64,
+                                       ctypes.POINTER(ctypes.c_double)]),
+    "crbm_null_ms": (_I32, [_H, _F]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@
 #include "crbm_sweep.h"
 #include "crbm_tsne.h"
 #include "crbm_background.h"
+#include "crbm_null.h"
 #include "../../include/crbm_amd.h"
 
 #include <dlfcn.h>
@@ -246,6 +247,7 @@ struct crbm_handle {
   bool slab_hgv = false;               // the chain's h|v takes the slabs too (slab a multiple of ten motifs, or one slab: sampler groups)
   uint64_t slab_tables_version = 0;
   float tsne_ms = 0.f;                 // device time of the iterations of the last crbm_tsne_descend call (HIP events)
+  float null_ms = 0.f;                 // device time of the kernels of the last crbm_score_distribution call
   float bg_ms = 0.f;                   // device time of the kernels of the last crbm_stream_kmer_counts / crbm_background_sample call
   std::string slab_note;               // why the slabs are off, if they are (crbm_launch_info prints nothing of it; a debugging aid)
   std::string err;
@@ -4054,6 +4056,84 @@ int crbm_background_sample(crbm_handle* h, const uint32_t* thr, int32_t order, i
 int crbm_background_ms(crbm_handle* h, float* ms) {
   if (!h || !ms) return CRBM_ERR_INVALID;
   *ms = h->bg_ms;
+  return CRBM_OK;
+}
+
+}  // extern "C"
+
+// ---- the analytic null (crbm_null.h): the handle lends its device, its main stream and its error string --------------
+extern "C" {
+
+int crbm_score_distribution(crbm_handle* h, const int32_t* q, int32_t R, int32_t M, int32_t order, const double* trans,
+                            const double* init, int64_t G, double* pmf) {
+  ENTER();
+  null::Plan plan;
+  if (const char* why = null::plan_or_refusal(q, R, M, order, trans, init, G, pmf, null::env_i64("CRBM_NULL_BYTES", null::BYTES_DEFAULT),
+                                              null::env_i64("CRBM_NULL_TILE", null::TILE_DEFAULT), &plan))
+    return fail(h, CRBM_ERR_INVALID, std::string("crbm_score_distribution: ") + why);
+  h->null_ms = 0.f;
+  const int NS = plan.contexts, variant = env_int("CRBM_NULL_VARIANT", null::VARIANT_DEFAULT), rpg = plan.rows_per_group;
+  std::vector<null::Pred> table((size_t)NS * null::PREDS);
+  null::build_table(order, trans, table.data());
+  TsneScratch s;
+  int32_t *dq = nullptr, *dreach = nullptr;
+  null::Pred* dtable = nullptr;
+  double *dinit = nullptr, *state[2] = {nullptr, nullptr}, *dpmf = nullptr;
+  HIPCHK(s.get(&dq, (size_t)R * M * 4));
+  HIPCHK(s.get(&dreach, (size_t)R * (M + 1)));
+  HIPCHK(s.get(&dtable, table.size()));
+  HIPCHK(s.get(&dinit, (size_t)NS));
+  HIPCHK(s.get(&state[0], (size_t)plan.state_elems));
+  HIPCHK(s.get(&state[1], (size_t)plan.state_elems));
+  HIPCHK(s.get(&dpmf, (size_t)rpg * (size_t)G));
+  BgEvents ev;
+  HIPCHK(ev.create());
+  const hipStream_t st = h->stream;
+  HIPCHK(hipMemcpyAsync(dq, q, (size_t)R * M * 16, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dreach, plan.reach.data(), (size_t)R * (M + 1) * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dtable, table.data(), table.size() * sizeof(null::Pred), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dinit, init, (size_t)NS * 8, hipMemcpyHostToDevice, st));
+  double device_ms = 0.0;
+  for (int row0 = 0; row0 < R; row0 += rpg) {
+    const int rows = std::min(rpg, R - row0);
+    HIPCHK(hipEventRecord(ev.t[0][0], st));
+    null::EdgeArgs e;
+    e.state = state[0]; e.init = dinit; e.pmf = dpmf; e.reach = dreach + (size_t)row0 * (M + 1);
+    e.gmax = plan.gmax; e.G = G; e.M = M; e.tile = plan.tile; e.contexts = NS; e.rows = rows;
+    hipLaunchKernelGGL(null::start_kernel, dim3((unsigned)grid_for((long)rows * NS, 256, 1 << 20)), dim3(256), 0, st, e);
+    for (int j = 0; j < M; ++j) {
+      null::Launch launches[2];
+      const int n = null::step_launches(plan, q, M, order, variant, row0, rows, j, launches);
+      for (int i = 0; i < n; ++i) {
+        const null::Launch& l = launches[i];
+        if (l.gy == 0) continue;
+        null::StepArgs a;
+        a.src = state[j & 1]; a.dst = state[(j & 1) ^ 1];
+        a.q = dq + (size_t)row0 * M * 4; a.reach = e.reach; a.table = dtable;
+        a.gmax = plan.gmax; a.M = M; a.j = j; a.tile = plan.tile; a.contexts = NS;
+        a.ctx0 = l.ctx0; a.nctx = l.nctx; a.lds_width = l.lds_width;
+        if (l.siblings) hipLaunchKernelGGL(null::step_siblings_kernel, dim3(l.gx, l.gy), dim3(l.block), l.lds, st, a);
+        else hipLaunchKernelGGL(null::step_plain_kernel, dim3(l.gx, l.gy), dim3(l.block), 0, st, a);
+      }
+    }
+    e.state = state[M & 1];
+    const unsigned mtiles = (unsigned)((G + plan.tile - 1) / plan.tile);
+    hipLaunchKernelGGL(null::marginal_kernel, dim3(mtiles, (unsigned)rows), dim3(null::block_for(plan.tile)), 0, st, e);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.t[0][1], st));
+    HIPCHK(hipMemcpyAsync(pmf + (size_t)row0 * (size_t)G, dpmf, (size_t)rows * (size_t)G * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev.t[0][0], ev.t[0][1]));
+    device_ms += ms;
+  }
+  h->null_ms = (float)device_ms;
+  return CRBM_OK;
+}
+
+int crbm_null_ms(crbm_handle* h, float* ms) {
+  if (!h || !ms) return CRBM_ERR_INVALID;
+  *ms = h->null_ms;
   return CRBM_OK;
 }
 

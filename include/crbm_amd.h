@@ -555,6 +555,34 @@ int crbm_background_sample(crbm_handle* h, const uint32_t* thr, int32_t order, i
                            uint64_t seed, const uint8_t* tmpl, uint8_t* out);
 int crbm_background_ms(crbm_handle* h, float* ms);
 
+/* ---- The analytic null: the exact distribution of a quantised window score under a Markov background ---------------
+ * Model-independent, like the Markov backgrounds above: the handle of any model lends its device, its main stream and
+ * its error string.  Every pointer is host memory; the call is complete when it returns.  (Additive: the ABI version
+ * stays.)
+ *
+ * crbm_score_distribution: R rows (a motif and strand each) of integer weights q (R, M, 4), q[r][j][a] >= 0 with
+ * min_a q[r][j][.] = 0; the integer score of a window a_0 .. a_{M-1} is Q = sum_j q[r][j][a_j], within [0, G_r),
+ * G_r = sum_j max_a q[r][j][.] + 1.  trans (contexts, 4) holds P(a | context) and init (contexts) the distribution of
+ * the context in front of the window, contexts indexed as above, partial contexts included (they are ordinary states:
+ * M < order + 1 is nothing special).  With next(s, a) the context behind s once a is appended:
+ *   f_0[s][0] = init[s];   f_{j+1}[s'][Q] = sum_{(s, a): next(s, a) = s'} trans[s][a] * f_j[s][Q - q[r][j][a]];
+ *   pmf[r][Q] = sum_s f_M[s][Q],   Q < G_r;   pmf[r][Q] = 0,   G_r <= Q < G.
+ * All float64, products and adds rounded separately; the (at most five) terms of a cell are added with s ascending,
+ * then a ascending, the contexts of the last sum in index order.  No atomics: the same inputs give the same bits
+ * whatever the tile length (CRBM_NULL_TILE, default 1024 cells), the grouping of rows (the two state buffers of a group
+ * of rows, 2 * contexts * max_r G_r * 8 bytes per row, stay within CRBM_NULL_BYTES, default 1 GiB) and the kernel
+ * variant (CRBM_NULL_VARIANT: 0 plain gather, 1 sibling contexts through the LDS).
+ * CRBM_ERR_INVALID, before anything is launched: a null pointer; R < 1; M outside [1, 512]; order outside [0, 3]; a
+ * negative q or a position whose smallest q is not 0; G below the largest G_r or above 2^24; an entry of trans or init
+ * that is negative or not finite; a row of trans that does not sum to 1 within 1e-9; a row whose state does not fit
+ * CRBM_NULL_BYTES (the message says to use a larger step).  pmf is not written then, and the handle stays usable.
+ *
+ * crbm_null_ms: device time (HIP events around the kernels of every group of rows, summed) of the handle's last
+ * crbm_score_distribution call. */
+int crbm_score_distribution(crbm_handle* h, const int32_t* q, int32_t R, int32_t M, int32_t order, const double* trans,
+                            const double* init, int64_t G, double* pmf);
+int crbm_null_ms(crbm_handle* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
