@@ -73,6 +73,16 @@ __device__ __forceinline__ uint32_t shl_or(uint32_t x, uint32_t acc) {
   return (x << SH) | acc;
 #endif
 }
+// a value that is the same in every lane of the wave, pinned to a scalar register at this point (no instruction): the
+// compiler can neither fold it into the vector expression it feeds nor pull a constant out of it (it moves constants
+// to the outermost xor of a chain, which turns scalar work back into vector work).  Only for wave-uniform values.
+__device__ __forceinline__ uint32_t uniform_word(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  x = __builtin_amdgcn_readfirstlane(x);     // folds away where x already sits in a scalar register
+  asm("" : "+s"(x));
+#endif
+  return x;
+}
 // max of four finite floats in two instructions (v_max3_f32, v_max_f32).  fmaxf puts a canonicalising v_max_f32 x, x
 // in front of every operand the compiler cannot prove canonical (a value that may come straight from memory); no
 // operand here is ever a NaN, and the result is the same number whatever the order (with zeros of both signs among
@@ -150,6 +160,7 @@ __device__ __forceinline__ floatx2 fma2(floatx2 a, floatx2 b, floatx2 c) { retur
 __device__ __forceinline__ floatx2 opaque(floatx2 v) { return v; }
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return a ^ b ^ c; }
 __device__ __forceinline__ float max4_finite(float a, float b, float c, float d) { return fmaxf(fmaxf(a, b), fmaxf(c, d)); }
+__device__ __forceinline__ uint32_t uniform_word(uint32_t x) { return x; }
 template <int SH> __device__ __forceinline__ uint32_t shl_or(uint32_t x, uint32_t acc) { return (x << SH) | acc; }
 __device__ __forceinline__ uint32_t bitrev32(uint32_t x) {
   x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
@@ -191,14 +202,44 @@ __device__ __forceinline__ floatx4 mfma_16x16x32_f16(const HalfFrag& a, const Ha
 #ifndef CRBM_PHILOX_ROUNDS
 #define CRBM_PHILOX_ROUNDS 7      // anything else (CRBM_JIT_DEFINES) is a timing experiment: the oracle draws seven
 #endif
+// A/B knobs of the second instruction diet (CRBM_JIT_DEFINES=-DCRBM_DIET2_<part>=0 takes one part out alone; every
+// part leaves every bit of every result as it is):
+//   CRBM_DIET2_A   sample_hidden: the exact path reads the coarse fields behind `opaque` (no register-pair copies)
+//   CRBM_DIET2_B   sample_hidden: coarse fields that do not straddle a word are converted where they sit
+//   CRBM_DIET2_C1  philox4x32<true>: the wave-uniform words of rounds 1-2 are joined on the scalar unit.  Not in the chain
+//                  kernel of models that defer their undecided units (gibbs_body, DEFER: double-stranded, unpooled):
+//                  there it was measured to COST time (config #5: 125.6-126.2 us per launch with it, 124.8-125.0
+//                  without, parent commit 126.2-126.9), so both call sites of that kernel take the plain form.
+#ifndef CRBM_DIET2_A
+#define CRBM_DIET2_A 1
+#endif
+#ifndef CRBM_DIET2_B
+#define CRBM_DIET2_B 1
+#endif
+#ifndef CRBM_DIET2_C1
+#define CRBM_DIET2_C1 1
+#endif
+// UNIFORM: c2, c3, k0 and k1 are the same in every lane of the wave (the counter word of a kind, the step, the seed:
+// every call site of a sampling pass), c0 and c1 (sequence, position) are not.  A v_bitop3_b32 takes ONE scalar
+// operand, so the three xors of rounds 1-2 that join two uniform words -- hi(M1 c2) ^ k0, c3 ^ k1 and, a round later,
+// lo(M1 c2) ^ (k0 + golden) -- each cost a v_mov_b32 of a scalar in front of them, inside the item loops.  Written as
+// x ^ uniform_word(u ^ u') the inner xor is scalar work and the outer one a v_xor_b32 with one scalar operand: the same
+// value (xor is associative), three vector instructions fewer per call.
+// CONTRACT of philox4x32<true>: c2, c3, k0 and k1 MUST be wave-uniform.  uniform_word reads them from the first active
+// lane, so a lane-varying word would give every lane that lane's stream, silently.  A caller whose kind, strand,
+// group, step or seed differs between the lanes of a wave takes philox4x32<false>.
+template <bool UNIFORM = false>
 __device__ __forceinline__ Philox4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                                  uint32_t k0, uint32_t k1) {
 #pragma unroll
   for (int r = 0; r < CRBM_PHILOX_ROUNDS; ++r) {
     const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
     const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
-    const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
+    const bool split = UNIFORM && CRBM_DIET2_C1;
+    const uint32_t n0 = split && r == 0 ? c1 ^ uniform_word((uint32_t)(p1 >> 32) ^ k0)
+                      : split && r == 1 ? (uint32_t)(p1 >> 32) ^ uniform_word(c1 ^ k0)
+                                        : xor3((uint32_t)(p1 >> 32), c1, k0);
+    const uint32_t n2 = split && r == 0 ? (uint32_t)(p0 >> 32) ^ uniform_word(c3 ^ k1) : xor3((uint32_t)(p0 >> 32), c3, k1);
     c1 = (uint32_t)p1;
     c3 = (uint32_t)p0;
     c0 = n0;
@@ -338,8 +379,30 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 // coarse = 0, whose sign only decides whether the exact path below is taken -- it returns 0 as well.
 __device__ __forceinline__ uint32_t shift_in_sign(uint32_t acc, float d) { return (acc << 1) | (__float_as_uint(d) >> 31); }
 
+// The coarse field as the two tests take it (CRBM_DIET2_B).  Only the SIGNS of d1 and d2 are used, a fused multiply-add
+// has the sign of its exact value, and an exact zero stays zero.  A field at bit b <= 20 of its word is converted
+// where it sits: (float)(word & (0xFFF << b)) is coarse * 2^b exactly (12 significant bits, nothing to round), and with
+// 4096 * 2^b and 2^b in place of 4096 and 1 the exact values of both forms are 2^b times those above -- the same signs
+// (the scaled values lie below 2^33 or round to an infinity of the same sign; nothing here can underflow).  One
+// mask and one conversion per field, no shift.
+// e = inf: (coarse + 1) 2^b > 0 gives d2 = -inf as before; coarse = 0 is 0 in both forms (d1 = NaN for e = inf, see
+// above; otherwise d1 = 4096 * 2^b > 0), and d2 = 2^b (4096 - (1 + e)) has the sign of 4096 - (1 + e).
+// The two fields that straddle a word boundary (2 and 5) keep philox_field12 and the scale 1.
+template <int I>
+struct CoarseField {
+  static constexpr int w = (12 * I) / 32, b = (12 * I) % 32;
+  static constexpr bool IN_PLACE = CRBM_DIET2_B && b <= 20;
+  static constexpr float SCALE = IN_PLACE ? (float)(1u << b) : 1.0f;
+  static __device__ __forceinline__ float get(const Philox4& r) {
+    if constexpr (IN_PLACE) return (float)(r.v[w] & (0xFFFu << b));
+    else return (float)philox_field12<I>(r);
+  }
+};
+
 // DEFER: the undecided units are not resolved here; their bits come back in pending[group] (mask has 0
 // there) and the caller resolves them later (gibbs_body queues them per block).
+// kind, strand, group0, step and rng's seed MUST be the same in every lane of the wave (philox4x32<true>'s contract,
+// above); n and s are per lane.
 template <class C, int WANT_P, bool DEFER = false>
 __device__ __forceinline__ void sample_hidden(const float (&z)[C::KP], uint32_t n, uint32_t s, uint32_t kind,
                                               uint32_t strand, const RngView& rng, uint32_t step,
@@ -349,10 +412,18 @@ __device__ __forceinline__ void sample_hidden(const float (&z)[C::KP], uint32_t 
   for (int w = 0; w < C::NW; ++w) mask[w] = 0u;
 #pragma unroll
   for (int g = 0; g < C::NGRP; ++g) {
-    const Philox4 rc = philox4x32(n, s, rng_word2(kind, strand, 0, group0 + (uint32_t)g), step, rng.seed_lo, rng.seed_hi);
+    const Philox4 rc = philox4x32<!DEFER>(n, s, rng_word2(kind, strand, 0, group0 + (uint32_t)g), step, rng.seed_lo, rng.seed_hi);   // DEFER: see CRBM_DIET2_C1
     constexpr int kFull = 10;
     const int cnt = C::K - 10 * g < kFull ? C::K - 10 * g : kFull;   // units of this group
     uint32_t not_one = 0u, zero = 0u;     // bit i: unit 10g+i is not certainly 1 / is certainly 0
+    // CRBM_DIET2_A: the converted fields as they stand behind `opaque`, for the exact path.  Converting them again there
+    // looks free but is not: the compiler merges that conversion with the one in front of `opaque`, keeps both copies
+    // of the pair alive and pays one v_mov_b64 per pair on the main path.
+    // How A and B meet: `pair` keeps in cf[i] what the tests took, coarse * CoarseField<i>::SCALE.  `fix` needs the
+    // unscaled field, so it reads cf[i] only where SCALE is 1 -- every slot without B, slots 2 and 5 (the fields that
+    // straddle a word) with B -- and extracts the field again, behind the branch, everywhere else; the slots it does
+    // not read cost nothing (dead stores of registers).  Without A, or under DEFER (no `fix`), cf is never written.
+    float cf[10];
     auto pair = [&](auto I) {             // units i + 1 and i of the group (i even), in that order
       constexpr int i = decltype(I)::value;
       const int k = 10 * g + i;
@@ -360,10 +431,13 @@ __device__ __forceinline__ void sample_hidden(const float (&z)[C::KP], uint32_t 
         const bool two = k + 1 < C::K;
         const floatx2 e = {exp_neg_x(z[k]), exp_neg_x(z[two ? k + 1 : k])};
         const floatx2 ope = e + 1.0f;
-        const floatx2 af = opaque(floatx2{(float)philox_field12<i>(rc), (float)philox_field12<i + 1>(rc)});
-        const floatx2 c4096 = {4096.0f, 4096.0f};
+        using F0 = CoarseField<i>;
+        using F1 = CoarseField<i + 1>;
+        const floatx2 af = opaque(floatx2{F0::get(rc), F1::get(rc)});            // coarse * SCALE
+        const floatx2 c4096 = {4096.0f * F0::SCALE, 4096.0f * F1::SCALE}, one = {F0::SCALE, F1::SCALE};
         const floatx2 d1 = fma2(-af, ope, c4096);             // >= 0: coarse (1 + e) <= 4096
-        const floatx2 d2 = fma2(-(af + 1.0f), ope, c4096);    // >= 0: (coarse + 1)(1 + e) <= 4096, h = 1
+        const floatx2 d2 = fma2(-(af + one), ope, c4096);     // >= 0: (coarse + 1)(1 + e) <= 4096, h = 1
+        if (CRBM_DIET2_A && !DEFER) { cf[i] = af[0]; cf[i + 1] = af[1]; }
         if (two) {
           zero = shift_in_sign(zero, d1[1]);
           not_one = shift_in_sign(not_one, d2[1]);
@@ -383,15 +457,18 @@ __device__ __forceinline__ void sample_hidden(const float (&z)[C::KP], uint32_t 
     const uint32_t amb = not_one & ~zero;   // units of this group that need the fine field
     if constexpr (DEFER) pending[g] = amb;
     if (!DEFER && __any(amb != 0u)) {
-      const Philox4 rf = philox4x32(n, s, rng_word2(kind, strand, 1, group0 + (uint32_t)g), step, rng.seed_lo, rng.seed_hi);
+      const Philox4 rf = philox4x32<true>(n, s, rng_word2(kind, strand, 1, group0 + (uint32_t)g), step, rng.seed_lo, rng.seed_hi);
       auto fix = [&](auto I) {
         constexpr int i = decltype(I)::value;
         const int k = 10 * g + i;
         if (k < C::K) {
           if (amb & (1u << i)) {
             // P*4096 - coarse lies in [0,1) up to rounding; compare with fine/4096
+            // (the unscaled field: the one kept by `pair` where its scale is 1, extracted again -- behind the
+            //  branch, and not the value the main path converts -- where it is not)
             const float t = 4096.0f * fast_rcp(1.0f + exp_neg_x(z[k]));
-            const float frac = t - (float)philox_field12<i>(rc);
+            const float coarse = CRBM_DIET2_A && CoarseField<i>::SCALE == 1.0f ? cf[i] : (float)philox_field12<i>(rc);
+            const float frac = t - coarse;
             ones |= (frac * 4096.0f > (float)philox_field12<i>(rf) ? 1u : 0u) << i;
           }
         }
@@ -1856,9 +1933,9 @@ __device__ void gibbs_body(const GibbsArgs& a, int bid = -1) {   // bid: block o
           }
         }
         // one Philox call serves the 4 positions of the block (convRBM.py:301-315)
-        const Philox4 r = philox4x32(a.rng.seq_offset + (uint32_t)(n0 + nl), (uint32_t)pb,
-                                        rng_word2(KIND_CHAIN_V, 0, 0, 0), a.rng.step + (uint32_t)st,
-                                        a.rng.seed_lo, a.rng.seed_hi);
+        const Philox4 r = philox4x32<!DEFER>(a.rng.seq_offset + (uint32_t)(n0 + nl), (uint32_t)pb,   // DEFER: see CRBM_DIET2_C1
+                                              rng_word2(KIND_CHAIN_V, 0, 0, 0), a.rng.step + (uint32_t)st,
+                                              a.rng.seed_lo, a.rng.seed_hi);
         uint32_t inv = 0u;
 #pragma unroll
         for (int i = 3; i >= 0; --i) inv = push_letter(inv, y[i][0], y[i][1], y[i][2], y[i][3], u01(r.v[i]));

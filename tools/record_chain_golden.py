@@ -29,9 +29,56 @@ SHAPES = [("ss_186_aligned", 10, 15, False, 186, 8, 4),     # the six of tests/t
           ("k16_exact", 16, 5, False, 20, 4, 2),            # four masks fill the 64 bits, none across bit 32
           ("k21_three", 21, 5, False, 20, 4, 2)]            # three masks per word, one across bit 32 (bits 21..41)
 LAUNCHES = (1, 1, 3)
+SAMPLER_SEED = 11      # the sampler seed (the Philox key) of every recorded chain
+
+# tests/golden/chain_exact_path.npz (tests/test_gpu_chain_exact_path.py): chains long enough that the exact path of the
+# hidden sampler -- entered by 2^-12 of all units -- sees every one of the ten 12-bit field slots of a Philox call, on
+# both strands where there are two.  The last entry is the sampler seed (the Philox key), chosen with exact_path_census
+# below on the CPU: tests/test_chain_exact_path_census.py holds the recorded run to at least two undecided units per slot.
+# __graft_entry__.EXACT_PATH_SHAPES compiles their kernels.
+EXACT_PATH_SHAPES = [("k10_ss_186_x32", 10, 15, False, 186, 32, 4, SAMPLER_SEED),    # the sampler resolves its units in the wave
+                     ("k21_ds_64_x32", 21, 8, True, 64, 32, 2, SAMPLER_SEED)]         # ... queues them per block; three groups, the last of one unit
+# the second shape once more with sample_hidden's own exact path in place of the block queue (crbm_kernels.h, gibbs_body)
+INLINE_EXACT_PATH_DEFINES = "-DCRBM_INLINE_EXACT_PATH"
 
 
-def run_chain(K, M, ds, Lf, B, S, geom):
+def chain_inputs(K, M, ds, Lf, B):
+    """Seeded parameters and start state of one shape: (W, b, c, h0, hp0), float32, hp0 None on one strand."""
+    rng = np.random.default_rng(9000 + 101 * K + 7 * M + Lf + B)
+    W = rng.standard_normal((K, 1, 4, M)).astype(np.float32)
+    b = (-3.0 + 0.5 * rng.standard_normal((1, K))).astype(np.float32)
+    c = (0.3 * rng.standard_normal((1, 4))).astype(np.float32)
+    h0 = rng.binomial(1, 0.08, size=(B, K, 1, Lf)).astype(np.float32)
+    hp0 = rng.binomial(1, 0.08, size=(B, K, 1, Lf)).astype(np.float32) if ds else None
+    return W, b, c, h0, hp0
+
+
+def exact_path_census(K, M, ds, Lf, B, seed=SAMPLER_SEED, steps=sum(LAUNCHES)):
+    """The undecided units of the same chain on the CPU, by the float64 oracle and its sampler: counts[strand, slot] of
+    the units whose coarse 12-bit field equals floor(4096 P) -- those the coarse tests of sample_hidden leave open --
+    over all steps of the launches; slot = unit % 10 is the field of the Philox call the unit draws."""
+    from oracle.crbm_oracle import OracleCRBM, hidden_uniforms, visible_uniforms, KIND_CHAIN_H, KIND_CHAIN_V
+    W, b, c, h, hp = chain_inputs(K, M, ds, Lf, B)
+    o = OracleCRBM(K, M, doublestranded=ds, batchsize=B, cd_k=1, fantasy_hidden_len=Lf, seed=seed, W=W)
+    o.b, o.c = b.astype(np.float64), c.astype(np.float64)
+    idx = np.arange(B)
+    counts = np.zeros((2 if ds else 1, 10), dtype=np.int64)
+    slot = np.arange(K) % 10
+    for t in range(steps):
+        _, v = o._computeVgivenH(h, hp, visible_uniforms(seed, t, idx, Lf + M - 1, KIND_CHAIN_V))
+        new = []
+        for strand in range(2 if ds else 1):
+            u = hidden_uniforms(seed, t, idx, K, Lf, strand, KIND_CHAIN_H)
+            P, hs = o._computeHgivenV(v, bool(strand), u)
+            coarse = np.floor(u * 4096.0)                     # u = (coarse * 4096 + fine) / 2^24
+            open_ = np.floor(P * 4096.0) == coarse
+            counts[strand] += np.bincount(np.broadcast_to(slot[None, :, None, None], open_.shape)[open_], minlength=10)
+            new.append(hs)
+        h, hp = new[0], (new[1] if ds else None)
+    return counts
+
+
+def run_chain(K, M, ds, Lf, B, S, geom, seed=SAMPLER_SEED):
     """The records of one shape in one geometry form: a dict of uint8 arrays, keys h<j>, hp<j> (packed bits) and v<j>
     (letters) after launch j."""
     from crbm_amd import CRBM
@@ -39,13 +86,11 @@ def run_chain(K, M, ds, Lf, B, S, geom):
     saved = {k: os.environ.get(k) for k in knobs}
     os.environ.update(knobs)
     try:
-        rng = np.random.default_rng(9000 + 101 * K + 7 * M + Lf + B)
-        model = CRBM(K, M, doublestranded=ds, batchsize=B, cd_k=1, fantasy_hidden_len=Lf, seed=11)
-        model.motifs.set_value(rng.standard_normal((K, 1, 4, M)).astype(np.float32))
-        model.bias.set_value((-3.0 + 0.5 * rng.standard_normal((1, K))).astype(np.float32).reshape(model.bias._shape))
-        model.c.set_value((0.3 * rng.standard_normal((1, 4))).astype(np.float32).reshape(model.c._shape))
-        h0 = rng.binomial(1, 0.08, size=(B, K, 1, Lf)).astype(np.float32)
-        hp0 = rng.binomial(1, 0.08, size=(B, K, 1, Lf)).astype(np.float32) if ds else None
+        W, b, c, h0, hp0 = chain_inputs(K, M, ds, Lf, B)
+        model = CRBM(K, M, doublestranded=ds, batchsize=B, cd_k=1, fantasy_hidden_len=Lf, seed=seed)
+        model.motifs.set_value(W)
+        model.bias.set_value(b.reshape(model.bias._shape))
+        model.c.set_value(c.reshape(model.c._shape))
         model.set_fantasy(h0, hp0)
         model.set_rng(gibbs_step=0)
         out = {}
@@ -69,10 +114,13 @@ def run_chain(K, M, ds, Lf, B, S, geom):
 
 
 def main():
-    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tests", "golden", "chain_parent.npz")
+    # python tools/record_chain_golden.py --exact-path [out.npz] records EXACT_PATH_SHAPES into chain_exact_path.npz
+    args = [a for a in sys.argv[1:] if a != "--exact-path"]
+    exact = len(args) != len(sys.argv) - 1
+    path = args[0] if args else os.path.join(ROOT, "tests", "golden", "chain_exact_path.npz" if exact else "chain_parent.npz")
     rec = {}
-    for name, K, M, ds, Lf, B, S in SHAPES:
-        ct, rt = run_chain(K, M, ds, Lf, B, S, 2), run_chain(K, M, ds, Lf, B, S, 0)
+    for name, K, M, ds, Lf, B, S, seed in (EXACT_PATH_SHAPES if exact else [s + (SAMPLER_SEED,) for s in SHAPES]):
+        ct, rt = run_chain(K, M, ds, Lf, B, S, 2, seed), run_chain(K, M, ds, Lf, B, S, 0, seed)
         assert ct.keys() == rt.keys() and all(np.array_equal(ct[k], rt[k]) for k in ct), name + ": the geometry forms differ"
         for k, a in ct.items():
             rec[name + "/" + k] = a
