@@ -143,6 +143,7 @@ SIGNATURES = {
     "crbm_copy_bandwidth": (_I32, [_H, ctypes.c_int64, _I32, _F]),
     "crbm_last_shader_clock": (_I32, [_H, _F]),
     "crbm_geometry_launches": (_I32, [_H, _I64P, _I64P]),
+    "crbm_live_resources": (_I32, [_I64P]),
     "crbm_gibbs_state_bytes": (ctypes.c_int64, [_H]),
     "crbm_tsne_neighbors": (_I32, [_H, _F, _I64, _I32, _I32, _I32P, _F]),
     "crbm_tsne_affinities": (_I32, [_H, _F, _I64, _I32, ctypes.c_float, _F, _F]),

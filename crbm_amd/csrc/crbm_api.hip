@@ -3,6 +3,7 @@
 // each entry point into kernel launches.  No torch, no Python types.
 #define CRBM_DEFINE_MISC_KERNELS
 #include "crbm_kernels.h"
+#include "crbm_own.h"
 #include "crbm_jit.h"
 #include "crbm_plan.h"
 #include "crbm_sweep.h"
@@ -18,6 +19,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <climits>
@@ -77,27 +79,6 @@ bool load_rccl() {
   return true;
 }
 
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;   // elements
-  hipError_t ensure(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = n + n / 8 + 64;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
 }  // namespace
 
 // The slab model of a generic DNA model (LaunchPlan::slab_K): its shape, its specialised kernels, the partial rows of its
@@ -128,17 +109,31 @@ struct PartWorker {
   hipError_t error = hipSuccess;
   int device = 0;
   hipStream_t stream = nullptr;
+  ~PartWorker() {                      // the thread enqueues the jobs it still holds, then ends
+    { std::lock_guard<std::mutex> lock(mu); stop = true; }
+    cv.notify_one();
+    if (th.joinable()) th.join();
+  }
+};
+// One partition beyond the first (partition 0 is the caller's thread on the handle's main stream and owns nothing here).
+// Members go in reverse: the thread is joined first -- nothing enqueues any more -- then the stream (synchronised), then the event.
+struct Partition {
+  Event done;
+  Stream stream;
+  std::unique_ptr<PartWorker> worker;
 };
 
+// Ownership: every GPU resource is a member that releases itself (crbm_own.h); crbm_destroy deletes the handle and names
+// none of them.  Members go in reverse order of declaration, so the order is part of the design: code objects and buffers
+// first, then events, streams and, last, the partitions.  Deleting a handle thus joins the partitions' threads, synchronises
+// and destroys their streams, then stream2 and stream, then the events, closes the mapped peer buffers and only then frees
+// buffers and unloads code objects: nothing goes while a stream may still run work that uses it.  New buffers: above `err`.
 struct crbm_handle {
   crbm_config cfg;
   int K = 0, M = 0, ds = 0, NW = 0, KAM = 0;
   int A = 4;                // letters of the alphabet (input_dims); anything but 4 runs on the generic kernels, rows of bytes
   int Lf = 0, Lv = 0, B = 0;
   int device = 0, num_cu = 256;
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;          // model phase of a training step runs beside the data phase
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
   bool overlap = false;
   // which kernels the model takes, the geometry of its chain launches, what its kernels are compiled with (crbm_plan.h:
   // the plan crbm_precompile compiled for); launches name the ChainGeom they mean, nothing here changes after crbm_create
@@ -146,18 +141,17 @@ struct crbm_handle {
   bool big() const { return plan.big; }              // the generic "big" kernels (crbm_kernels.h) serve every entry point
   const ModelShape& ms() const { return plan.ms; }
   JitKernels jk;            // kernels specialised for this model (hiprtc)
-  float* d_tables = nullptr;   // precomputed LDS images (gather / top-down tables, c)
-  float* d_tf_solo = nullptr;  // gather table in the solo grouping (plan.GS != plan.G only), rebuilt lazily before a plain chain launch
+  DevBuf<float> d_tables;      // precomputed LDS images (gather / top-down tables, c)
+  DevBuf<float> d_tf_solo;     // gather table in the solo grouping (plan.GS != plan.G only), rebuilt lazily before a plain chain launch
   bool tables_dirty = true;
   uint64_t params_version = 1, tf_solo_version = 0;   // bumped with every change of W, b, c / version d_tf_solo was built from
   // parameters and optimiser state
-  float *dW = nullptr, *db = nullptr, *dc = nullptr, *dvW = nullptr, *dvb = nullptr, *dvc = nullptr;
+  DevBuf<float> dW, db, dc, dvW, dvb, dvc;
   // the update writes into a second set of buffers; the two sets swap after every step (launch_update)
-  float *dW2 = nullptr, *db2 = nullptr, *dc2 = nullptr, *dvW2 = nullptr, *dvb2 = nullptr, *dvc2 = nullptr;
+  DevBuf<float> dW2, db2, dc2, dvW2, dvb2, dvc2;
   // persistent chains: K-bit masks per hidden position, letters of the last visible sample
-  uint32_t *d_hm = nullptr, *d_hmp = nullptr, *d_vf = nullptr;
-  uint32_t* d_flags = nullptr;
-  unsigned long long* d_ones = nullptr;
+  DevBuf<uint32_t> d_hm, d_hmp, d_vf, d_flags;
+  DevBuf<unsigned long long> d_ones;
   DevBuf<float> stage, stage2, out_a, out_b, out_c;
   DevBuf<uint32_t> letters, letters2, masks_tmp;   // (…2: second set of the double-buffered host-input sweeps)
   DevBuf<float> out_a2, out_b2;
@@ -187,18 +181,14 @@ struct crbm_handle {
   // and the device copy of rec_start; both streams add into the accumulators
   DevBuf<unsigned long long> rec_acc;
   DevBuf<long long> rec_start;
-  float* d_sums = nullptr;
+  DevBuf<float> d_sums;
   int dataset_n[CRBM_DATASET_SLOTS] = {0, 0}, dataset_L[CRBM_DATASET_SLOTS] = {0, 0};
   int slot = 0;
   // sampler
   uint64_t seed = 0;
   uint32_t gibbs_step = 0, eval_step = 0, chain_offset = 0;
   int LWs = 0;                         // words per row of the last visible sample (d_vf)
-  // the streams, threads and events of the partitions of plain chain launches (plan.chain_parts > 1)
-  hipStream_t part_stream[4] = {nullptr, nullptr, nullptr, nullptr};
-  PartWorker* part_worker[4] = {nullptr, nullptr, nullptr, nullptr};   // [0] stays null: the caller's thread
-  hipEvent_t part_done[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_parts_fork = nullptr;
+  // the partitions of plain chain launches (plan.chain_parts > 1): `part`, at the end
   bool forked = false;                 // the partition streams hold work the main stream has not waited for yet
   bool main_idle_hint = false;         // the main stream was idle when the caller last looked (only its own event record is pending)
   // Partitions that start together stay in lockstep for hundreds of launches -- their gaps coincide and nothing is
@@ -206,12 +196,11 @@ struct crbm_handle {
   // So partition p starts p/P of a launch late: a one-wave delay kernel in front of its first launch after a fork.
   // The length of a launch is measured on the way (events around partition 0's first launch of the previous fork).
   double part_launch_us = 0.0;         // 0: not known yet (cost model below)
-  hipEvent_t ev_cal0 = nullptr, ev_cal1 = nullptr;
   bool cal_pending = false;
   int wall_khz = 100000;               // ticks of the GPU's wall clock per millisecond
   int variant = 1;                     // top-down variant of the Gibbs kernel in use (plan.chain[variant]; fixed per handle)
   int topdown_mode = 0;                // CRBM_TOPDOWN: 1 dense, anything else the set-bit walk (fixed per handle)
-  uint32_t* d_nset = nullptr;          // per wave of the last Gibbs launch: set bits of the final state
+  DevBuf<uint32_t> d_nset;             // per wave of the last Gibbs launch: set bits of the final state
   int nset_slots = 0;
   uint32_t launches_since_read = 0;
   double activity = -1.0;              // fraction of hidden units on after the last launch that was read back
@@ -223,26 +212,26 @@ struct crbm_handle {
   ncclComm_t comm = nullptr;
   int nranks = 1, rank = 0;
   // ... without a collective launch: every rank's sums buffer mapped into every rank (crbm_ipc_*)
-  float* ipc_buf = nullptr;            // own: [2 parities][ipc_stride floats], then 2 flag words and a status word
-  void* ipc_peer[IPC_MAX_RANKS] = {};  // all ranks' buffers as this process sees them (own included)
+  DevBuf<float> ipc_buf;               // own: [2 parities][ipc_stride floats], then 2 flag words and a status word
   int ipc_stride = 0;                  // floats per parity (sums count rounded up to a 128-byte line)
   bool ipc_on = false;
   uint32_t ipc_step = 0;               // steps published so far (the flag value of the next one is ipc_step + 1)
   bool ipc_published = false;          // the column reduction of the running step has written and flagged the published buffer itself
-  uint32_t* d_ticket = nullptr;        // arrival counter of that launch (zero between launches)
-  unsigned long long* d_probe = nullptr;   // {wall ticks, shader cycles, scratch, scratch} summed over the launches of all crbm_time_gibbs calls
+  DevBuf<uint32_t> d_ticket;           // arrival counter of that launch (zero between launches)
+  DevBuf<unsigned long long> d_probe;      // {wall ticks, shader cycles, scratch, scratch} summed over the launches of all crbm_time_gibbs calls
   unsigned long long probe_base[2] = {0, 0}, probe_last[2] = {0, 0};   // the sums before / after the last call
   bool probe_on = false;
   JitGeoKernels jg;             // the chain kernels compiled for the plan's launch shapes (LaunchPlan::geo_plain / geo_fused)
   long long geo_launches[2] = {0, 0};   // chain kernel launches in the run-time form, with the geometry compiled in (crbm_geometry_launches)
-  unsigned long long* d_timeline = nullptr;   // CRBM_GIBBS_TIMELINE: first / last tick of block 0 of every launch of a crbm_time_gibbs call
-  int timeline_cap = 0, timeline_next = 0;
+  DevBuf<unsigned long long> d_timeline;      // CRBM_GIBBS_TIMELINE: first / last tick of block 0 of every launch of a crbm_time_gibbs call
+  int timeline_next = 0;
+  int timeline_cap() const { return (int)(d_timeline.cap / 2); }      // launches the buffer has slots for
   unsigned long long ipc_timeout_ticks = 0;   // bound of an update launch's wait for its peers, in ticks of the GPU's wall clock
   // Statistics, h|v, free energies and site scans of a generic DNA model on the specialised kernels, a slab of motifs
   // at a time: the slab model (slab.K motifs; 0: none, slab_note says why) and one table image per slab, rebuilt when
   // the parameters have changed
   SlabModel slab;
-  float* d_slab_tables = nullptr;
+  DevBuf<float> d_slab_tables;
   int slab_n = 0;
   bool slab_hgv = false;               // the chain's h|v takes the slabs too (slab a multiple of ten motifs, or one slab: sampler groups)
   uint64_t slab_tables_version = 0;
@@ -251,6 +240,12 @@ struct crbm_handle {
   float bg_ms = 0.f;                   // device time of the kernels of the last crbm_stream_kmer_counts / crbm_background_sample call
   std::string slab_note;               // why the slabs are off, if they are (crbm_launch_info prints nothing of it; a debugging aid)
   std::string err;
+  PeerMaps<IPC_MAX_RANKS> ipc_peer;    // all ranks' buffers as this process sees them (own included: ipc_buf)
+  Event ev0, ev1, ev_fork, ev_join, ev_parts_fork;
+  Event ev_cal0, ev_cal1;              // around partition 0's first launch of a fork (part_launch_us)
+  Stream stream;
+  Stream stream2;                      // model phase of a training step runs beside the data phase
+  Partition part[4];                   // the streams, threads and events of the partitions of plain chain launches
 };
 
 namespace {
@@ -290,7 +285,7 @@ int lw(const crbm_handle* h, int L) { return letter_words_any(h->A, L); }
 int ensure_tables(crbm_handle* h) {
   if (!h->tables_dirty || h->big()) return CRBM_OK;
   TablesArgs t;
-  t.W = h->dW; t.b = h->db; t.c = h->dc; t.out = h->d_tables;
+  t.W = h->dW.p; t.b = h->db.p; t.c = h->dc.p; t.out = h->d_tables.p;
   const unsigned grid = (unsigned)std::max(1, std::min((h->ms().TABLES_ALL + 255) / 256, h->num_cu * 4));
   HIPCHK(jit_launch(h->jk.build_tables, t, grid, 1, 256, 0, h->stream));
   h->tables_dirty = false;
@@ -302,7 +297,7 @@ int ensure_tables(crbm_handle* h) {
 int ensure_solo_table(crbm_handle* h) {
   if (h->plan.GS == h->plan.G || h->tf_solo_version == h->params_version) return CRBM_OK;
   TablesArgs t;
-  t.W = h->dW; t.b = h->db; t.c = h->dc; t.out = h->d_tf_solo;
+  t.W = h->dW.p; t.b = h->db.p; t.c = h->dc.p; t.out = h->d_tf_solo.p;
   const unsigned grid = (unsigned)std::max(1, std::min((h->plan.ms_solo.TAB + 255) / 256, h->num_cu * 4));
   HIPCHK(jit_launch(h->jk.build_gather_solo, t, grid, 1, 256, 0, h->stream));
   h->tf_solo_version = h->params_version;
@@ -313,7 +308,7 @@ int ensure_solo_table(crbm_handle* h) {
 // ---- the "big" path (crbm_kernels.h: models beyond the LDS-resident kernels) --------------------------------------
 BigModel big_model(const crbm_handle* h) {
   BigModel m;
-  m.W = h->dW; m.b = h->db; m.c = h->dc;
+  m.W = h->dW.p; m.b = h->db.p; m.c = h->dc.p;
   m.K = h->K; m.M = h->M; m.ds = h->ds; m.NW = h->NW; m.A = h->A;
   return m;
 }
@@ -369,12 +364,12 @@ int big_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int 
 int big_launch_gibbs(crbm_handle* h, int steps, hipStream_t st) {
   BigVghArgs v;
   v.m = big_model(h);
-  v.hm = h->d_hm; v.hmp = h->ds ? h->d_hmp : nullptr; v.vout = h->d_vf;
+  v.hm = h->d_hm.p; v.hmp = h->ds ? h->d_hmp.p : nullptr; v.vout = h->d_vf.p;
   v.nchains = h->B; v.Lf = h->Lf; v.Lv = h->Lv; v.LWs = h->LWs;
   const BigVghGeom g = big_vgh_geom(h->A, h->M, h->Lv);      // (crbm_plan.h)
   v.JS = g.JS;
   const size_t lds = g.lds;
-  HIPCHK(hipMemsetAsync(h->d_ones, 0, sizeof(unsigned long long), st));
+  HIPCHK(hipMemsetAsync(h->d_ones.p, 0, sizeof(unsigned long long), st));
   for (int t = 0; t < steps; ++t) {
     v.rng = rng_view(h, h->gibbs_step + (uint32_t)t, h->chain_offset);
     if (h->A == 4) hipLaunchKernelGGL(big_vgh_kernel, dim3(std::max(1, std::min(h->B, h->num_cu * 8))), dim3(256), lds, st, v);
@@ -382,8 +377,8 @@ int big_launch_gibbs(crbm_handle* h, int steps, hipStream_t st) {
     HIPCHK(hipGetLastError());
     const bool last = t == steps - 1;      // the last step also counts the units that are on (activity monitor)
     for (int strand = 0; strand <= h->ds; ++strand) {
-      const int rc = big_launch_hgv(h, h->d_vf, h->B, h->Lv, strand, nullptr, nullptr, nullptr, last ? h->d_ones : nullptr,
-                                    strand ? h->d_hmp : h->d_hm, KIND_CHAIN_H, h->gibbs_step + (uint32_t)t, h->chain_offset, st);
+      const int rc = big_launch_hgv(h, h->d_vf.p, h->B, h->Lv, strand, nullptr, nullptr, nullptr, last ? h->d_ones.p : nullptr,
+                                    strand ? h->d_hmp.p : h->d_hm.p, KIND_CHAIN_H, h->gibbs_step + (uint32_t)t, h->chain_offset, st);
       if (rc) return rc;
     }
   }
@@ -399,7 +394,7 @@ ReduceArgs reduce_args(const crbm_handle* h, bool data_half, float* partials, in
   r.partials = partials;
   r.nrows = nrows; r.row = row;
   r.K = h->K; r.KAM = h->KAM; r.ds = h->ds; r.want_sparsity = data_half ? 1 : 0;
-  r.sums = h->d_sums + (data_half ? h->sl.data_off : h->sl.model_off);
+  r.sums = h->d_sums.p + (data_half ? h->sl.data_off : h->sl.model_off);
   r.skip_begin = data_half ? row : h->sl.model_skip_begin;      // (sw, sb are not carried for the model half)
   r.skip_len = data_half ? 0 : h->sl.model_skip_len;
   r.n_value = (float)n;
@@ -468,10 +463,10 @@ int tile_seqs(int len, int target) { return std::max(1, std::min(target / std::m
 
 int check_flags(crbm_handle* h) {
   uint32_t flags = 0;
-  HIPCHK(hipMemcpyAsync(&flags, h->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&flags, h->d_flags.p, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   if (flags) {
-    HIPCHK(hipMemsetAsync(h->d_flags, 0, sizeof(uint32_t), h->stream));
+    HIPCHK(hipMemsetAsync(h->d_flags.p, 0, sizeof(uint32_t), h->stream));
     if (flags & 1u) return fail(h, CRBM_ERR_NOT_ONEHOT, "visible data is not exactly one-hot");
     return fail(h, CRBM_ERR_NOT_BINARY, "hidden state is not exactly 0/1");
   }
@@ -484,7 +479,7 @@ int launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int mode
   int rc = ensure_tables(h);
   if (rc) return rc;
   HgvArgs a;
-  a.tables = h->d_tables;
+  a.tables = h->d_tables.p;
   a.letters = d_letters;
   a.n = n; a.L = L; a.Lh = L - h->M + 1; a.LW = lw(h, L);
   a.TS = tile_seqs(a.Lh, 4096);
@@ -523,9 +518,9 @@ hipFunction_t geo_kernel(const GeoSpec& spec, hipFunction_t fn, const ChainGeom&
 int prepare_gibbs(crbm_handle* h, const ChainGeom& g, int steps, ReduceArgs* model_reduce, GibbsArgs* out, unsigned* lds_out) {
   const GibbsLayout& gl = g.gl;
   GibbsArgs& a = *out;
-  a.tables = h->d_tables;
+  a.tables = h->d_tables.p;
   a.tables_tf = nullptr; a.off_ws = 0;
-  a.hm = h->d_hm; a.hmp = h->ds ? h->d_hmp : nullptr; a.vout = h->d_vf;
+  a.hm = h->d_hm.p; a.hmp = h->ds ? h->d_hmp.p : nullptr; a.vout = h->d_vf.p;
   a.nchains = h->B; a.Lf = h->Lf; a.Lv = gl.Lv; a.S = gl.S;
   a.nvb = gl.nvb; a.nhb = gl.nhb; a.Lrow = gl.Lrow; a.LWs = gl.LWs;
   a.divVB = make_fastdiv((uint32_t)a.nvb);
@@ -534,8 +529,8 @@ int prepare_gibbs(crbm_handle* h, const ChainGeom& g, int steps, ReduceArgs* mod
   a.divLfw = make_fastdiv((uint32_t)(a.Lf * h->NW));
   a.steps = steps;
   a.rng = rng_view(h, h->gibbs_step, h->chain_offset);
-  a.ones = h->d_nset;
-  a.clock = h->probe_on ? h->d_probe : nullptr;
+  a.ones = h->d_nset.p;
+  a.clock = h->probe_on ? h->d_probe.p : nullptr;
   a.timeline = nullptr;
   a.debug = env_int("CRBM_GIBBS_DEBUG", 0);
   a.nblocks = g.grid;
@@ -588,7 +583,7 @@ void part_worker_main(PartWorker* w) {
 // every launch handed to the partitions' threads has been enqueued on its stream
 int drain_part_workers(crbm_handle* h) {
   for (int p = 1; p < h->plan.chain_parts; ++p) {
-    PartWorker* w = h->part_worker[p];
+    PartWorker* w = h->part[p].worker.get();
     if (!w) continue;
     std::unique_lock<std::mutex> lock(w->mu);
     w->idle_cv.wait(lock, [&] { return w->jobs.empty() && !w->busy; });
@@ -609,8 +604,8 @@ int join_parts(crbm_handle* h) {
     if (rc) return rc;
   }
   for (int p = 1; p < h->plan.chain_parts; ++p) {          // (partition 0 is the main stream itself)
-    HIPCHK(hipEventRecord(h->part_done[p], h->part_stream[p]));
-    HIPCHK(hipStreamWaitEvent(h->stream, h->part_done[p], 0));
+    HIPCHK(hipEventRecord(h->part[p].done, h->part[p].stream));
+    HIPCHK(hipStreamWaitEvent(h->stream, h->part[p].done, 0));
   }
   h->forked = false;
   return CRBM_OK;
@@ -624,7 +619,7 @@ int launch_gibbs_parts(crbm_handle* h, int steps) {
     if (!h->main_idle_hint && hipStreamQuery(h->stream) != hipSuccess) {     // ... unless it is idle: nothing to wait for, no cross-stream dependency to resolve
       (void)hipGetLastError();
       HIPCHK(hipEventRecord(h->ev_parts_fork, h->stream));
-      for (int p = 1; p < h->plan.chain_parts; ++p) HIPCHK(hipStreamWaitEvent(h->part_stream[p], h->ev_parts_fork, 0));
+      for (int p = 1; p < h->plan.chain_parts; ++p) HIPCHK(hipStreamWaitEvent(h->part[p].stream, h->ev_parts_fork, 0));
     }
     h->main_idle_hint = false;
     h->forked = true;
@@ -662,13 +657,13 @@ int launch_gibbs_parts(crbm_handle* h, int steps) {
     ap.rng.seq_offset = a.rng.seq_offset + (uint32_t)c0;
     ap.ones = a.ones + (size_t)p * grid * waves;
     if (p > 0) ap.clock = nullptr;
-    if (h->d_timeline && h->timeline_next < h->timeline_cap) ap.timeline = h->d_timeline + 2 * (size_t)(h->timeline_next++);
+    if (h->d_timeline.p && h->timeline_next < h->timeline_cap()) ap.timeline = h->d_timeline.p + 2 * (size_t)(h->timeline_next++);
     ap.nblocks = (int)grid;
     hipFunction_t fn = geo_kernel(plan.geo_plain, h->jg.gibbs_sparse, plan.part, ap);
     h->geo_launches[fn ? 1 : 0] += 1;
     if (!fn) fn = h->jk.gibbs_sparse;
     if (p > 0) {          // the partition's own thread enqueues it
-      PartWorker* w = h->part_worker[p];
+      PartWorker* w = h->part[p].worker.get();
       {
         std::lock_guard<std::mutex> lock(w->mu);
         w->jobs.push_back(PartJob{fn, ap, grid, threads, lds, (unsigned long long)(stagger_ticks * p)});
@@ -677,10 +672,10 @@ int launch_gibbs_parts(crbm_handle* h, int steps) {
       continue;
     }
     const bool calibrate = first_of_fork && !h->cal_pending;
-    if (calibrate) HIPCHK(hipEventRecord(h->ev_cal0, h->part_stream[0]));
-    HIPCHK(jit_launch(fn, ap, grid, 1, threads, lds, h->part_stream[0]));
+    if (calibrate) HIPCHK(hipEventRecord(h->ev_cal0, h->stream));
+    HIPCHK(jit_launch(fn, ap, grid, 1, threads, lds, h->stream));
     if (calibrate) {
-      HIPCHK(hipEventRecord(h->ev_cal1, h->part_stream[0]));
+      HIPCHK(hipEventRecord(h->ev_cal1, h->stream));
       h->cal_pending = true;
     }
   }
@@ -703,12 +698,12 @@ int launch_gibbs(crbm_handle* h, int steps, hipStream_t s = nullptr, ReduceArgs*
   unsigned lds = 0;
   rc = prepare_gibbs(h, g, steps, model_reduce, &a, &lds);
   if (!model_reduce && h->variant == 1 && h->plan.GS != h->plan.G) {     // crbm_gibbs_sparse is compiled for the solo grouping
-    a.tables_tf = h->d_tf_solo; a.off_ws = h->ms().OFF_WS;
+    a.tables_tf = h->d_tf_solo.p; a.off_ws = h->ms().OFF_WS;
     if (rc == CRBM_OK) rc = ensure_solo_table(h);
   }
   if (rc) return rc;
   h->nset_slots = g.grid * (g.threads / 64);
-  if (plain && h->d_timeline && h->timeline_next < h->timeline_cap) a.timeline = h->d_timeline + 2 * (size_t)(h->timeline_next++);
+  if (plain && h->d_timeline.p && h->timeline_next < h->timeline_cap()) a.timeline = h->d_timeline.p + 2 * (size_t)(h->timeline_next++);
   hipFunction_t fn = model_reduce ? h->jk.gibbs_sparse_stats : (h->variant ? h->jk.gibbs_sparse : h->jk.gibbs);
   if (h->variant == 1) {
     hipFunction_t geo = model_reduce ? geo_kernel(h->plan.geo_fused, h->jg.gibbs_sparse_stats, g, a)
@@ -731,13 +726,13 @@ int refresh_activity(crbm_handle* h) {
   if (h->launches_since_read == 0) return CRBM_OK;
   if (h->big()) {          // the last step's h|v launches counted into d_ones
     unsigned long long on = 0;
-    HIPCHK(hipMemcpy(&on, h->d_ones, sizeof(on), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&on, h->d_ones.p, sizeof(on), hipMemcpyDeviceToHost));
     h->launches_since_read = 0;
     h->activity = (double)on / ((double)h->B * h->Lf * h->K * (1 + h->ds));
     return CRBM_OK;
   }
   std::vector<uint32_t> slots((size_t)h->nset_slots);
-  HIPCHK(hipMemcpy(slots.data(), h->d_nset, slots.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(slots.data(), h->d_nset.p, slots.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
   unsigned long long last = 0;
   for (uint32_t v : slots) last += v;
   h->launches_since_read = 0;
@@ -827,7 +822,7 @@ int slab_ensure_tables(crbm_handle* h, hipStream_t st) {
   const SlabModel* s = &h->slab;
   if (h->slab_tables_version == h->params_version) return CRBM_OK;
   SlabTablesArgs a;
-  a.t.W = h->dW; a.t.b = h->db; a.t.c = h->dc; a.t.out = h->d_slab_tables;
+  a.t.W = h->dW.p; a.t.b = h->db.p; a.t.c = h->dc.p; a.t.out = h->d_slab_tables.p;
   a.plan = slab_plan(h);
   a.stride = s->ms.TABLES_ALL;
   const unsigned grid = (unsigned)std::max(1, std::min((s->ms.TABLES_ALL + 255) / 256, h->num_cu * 4));
@@ -850,7 +845,7 @@ int slab_launch_hgv(crbm_handle* h, const uint32_t* d_letters, int n, int L, int
   HIPCHK(hipMemsetAsync(masks, 0, (size_t)n * Lh * h->NW * sizeof(uint32_t), st));
   SlabHgvArgs sa;
   HgvArgs& a = sa.m.g;
-  a.tables = h->d_slab_tables;
+  a.tables = h->d_slab_tables.p;
   a.letters = d_letters;
   a.n = n; a.L = L; a.Lh = Lh; a.LW = lw(h, L);
   // rows per tile: ~4096 positions, fewer for small batches (enough blocks, with the slabs, to cover the chip a few times over)
@@ -881,7 +876,7 @@ int slab_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, b
   DevBuf<float>& pbuf = data_half ? s->partials : s->partials2;
   SlabStatsArgs sa;
   StatsLaunch l;
-  rc = prepare_stats(h, s->ms, h->d_slab_tables, pbuf, d_letters, n, L, data_half, 0, &sa.a, &l);
+  rc = prepare_stats(h, s->ms, h->d_slab_tables.p, pbuf, d_letters, n, L, data_half, 0, &sa.a, &l);
   if (rc == CRBM_ERR_INVALID) {      // (a data set whose rows the slab kernel's LDS does not take)
     h->err.clear();
     return SLAB_FALLBACK;
@@ -896,7 +891,7 @@ int slab_launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, b
     return fail(h, CRBM_ERR_HIP, "launch of the slab statistics kernel failed");
   SlabReduceArgs ra;
   ra.partials = pbuf.p;
-  ra.sums = h->d_sums + (data_half ? h->sl.data_off : h->sl.model_off);
+  ra.sums = h->d_sums.p + (data_half ? h->sl.data_off : h->sl.model_off);
   ra.nrows = l.grid; ra.row = l.row;
   ra.Ks = Ks; ra.k0 = slab_origin(h, h->slab_n - 1); ra.K = h->K; ra.M4 = 4 * M;
   ra.partial_stride = (long long)per_slab;
@@ -924,7 +919,7 @@ int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe
   const size_t per_slab = (size_t)n * s->K;
   HIPCHK(scratch->ensure(per_slab * h->slab_n));
   SlabFeArgs sa;
-  sa.a.tables = h->d_slab_tables;
+  sa.a.tables = h->d_slab_tables.p;
   sa.a.letters = rows;
   sa.a.n = n; sa.a.L = L; sa.a.Lh = L - h->M + 1; sa.a.LW = lw(h, L);
   sa.a.fe = nullptr; sa.a.fem = scratch->p;
@@ -934,7 +929,7 @@ int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe
   HIPCHK(jit_launch(s->jk.slab_fe, sa, gx, (unsigned)h->slab_n, 256, (unsigned)tab_bytes(s->ms), st));
   SlabFeCombineArgs ca;
   ca.scratch = scratch->p;
-  ca.c_log2e = h->d_slab_tables + s->ms.OFF_C;
+  ca.c_log2e = h->d_slab_tables.p + s->ms.OFF_C;
   ca.letters = rows;
   ca.n = n; ca.L = L; ca.LW = lw(h, L);
   ca.Ks = s->K; ca.K = h->K; ca.last_k0 = slab_origin(h, h->slab_n - 1); ca.nslab = h->slab_n;
@@ -942,14 +937,6 @@ int slab_launch_fe(crbm_handle* h, const uint32_t* rows, int n, int L, float* fe
   hipLaunchKernelGGL(slab_fe_combine_kernel, dim3(gx), dim3(256), 0, st, ca);
   HIPCHK(hipGetLastError());
   return CRBM_OK;
-}
-
-void slab_destroy(crbm_handle* h) {
-  SlabModel* s = &h->slab;
-  s->partials.release(); s->partials2.release(); s->fe_scratch[0].release(); s->fe_scratch[1].release();
-  if (s->jk.module) (void)hipModuleUnload(s->jk.module);
-  s->jk = JitKernels();
-  if (h->d_slab_tables) { (void)hipFree(h->d_slab_tables); h->d_slab_tables = nullptr; }
 }
 
 // The slab model of a generic handle (crbm_create), as the plan chose it; leaves h->slab.K zero, with the reason in
@@ -961,14 +948,12 @@ void slab_setup(crbm_handle* h) {
   const int n = (h->K + plan.slab_K - 1) / plan.slab_K;
   std::string err;
   if (jit_load(plan.slab_K, h->M, h->ds, plan.slab_G, plan.slab_G, plan.slab_ms.POOL, 0, 256, &h->slab.jk, &err, true) != 0) {
-    slab_destroy(h);
     h->slab_note = "kernel specialisation of the slab failed: " + err;
     return;
   }
-  if (hipMalloc((void**)&h->d_slab_tables, (size_t)n * plan.slab_ms.TABLES_ALL * 4) != hipSuccess) {
+  if (h->d_slab_tables.alloc((size_t)n * plan.slab_ms.TABLES_ALL) != hipSuccess) {
     (void)hipGetLastError();
-    h->d_slab_tables = nullptr;
-    slab_destroy(h);
+    h->slab = SlabModel();
     h->slab_note = "no memory for the slab tables";
     return;
   }
@@ -990,7 +975,7 @@ int launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool d
     StatsMfmaArgs a;
     StatsLaunch l;
     DevBuf<float>& pbuf = data_half ? h->partials : h->partials2;
-    rc = prepare_stats(h, h->ms(), h->d_tables, pbuf, d_letters, n, L, data_half, 0, &a, &l);
+    rc = prepare_stats(h, h->ms(), h->d_tables.p, pbuf, d_letters, n, L, data_half, 0, &a, &l);
     if (rc) return rc;
     r = reduce_args(h, data_half, pbuf.p, l.grid, l.row, n);
     rc = jit_launch(data_half ? h->jk.stats_mfma_data : h->jk.stats_mfma_model, a, (unsigned)l.grid, 1, (unsigned)l.block, (unsigned)l.lds, s) == hipSuccess
@@ -1006,21 +991,21 @@ int launch_stats(crbm_handle* h, const uint32_t* d_letters, int n, int L, bool d
 
 void fill_update_args(crbm_handle* h, int L_data, UpdateTablesArgs& a) {
   UpdateArgs& u = a.u;
-  u.sums = h->d_sums;
-  u.W = h->dW; u.b = h->db; u.c = h->dc; u.vW = h->dvW; u.vb = h->dvb; u.vc = h->dvc;
-  u.oW = h->dW2; u.ob = h->db2; u.oc = h->dc2; u.ovW = h->dvW2; u.ovb = h->dvb2; u.ovc = h->dvc2;
+  u.sums = h->d_sums.p;
+  u.W = h->dW.p; u.b = h->db.p; u.c = h->dc.p; u.vW = h->dvW.p; u.vb = h->dvb.p; u.vc = h->dvc.p;
+  u.oW = h->dW2.p; u.ob = h->db2.p; u.oc = h->dc2.p; u.ovW = h->dvW2.p; u.ovb = h->dvb2.p; u.ovc = h->dvc2.p;
   u.K = h->K; u.M = h->M; u.ds = h->ds;
   u.L_data = L_data; u.Lf = h->Lf;
   u.data_off = h->sl.data_off; u.n_d = h->sl.n_d; u.model_off = h->sl.model_off; u.n_m = h->sl.n_m;
   u.lr = h->cfg.learning_rate; u.momentum = h->cfg.momentum; u.rho = h->cfg.rho; u.lambda_rate = h->cfg.lambda_rate;
   u.A = h->A;
-  a.tables = h->d_tables;
+  a.tables = h->d_tables.p;
 }
 
 // the update wrote the other set of buffers: it is the current one from now on
 void swap_param_sets(crbm_handle* h) {
-  std::swap(h->dW, h->dW2); std::swap(h->db, h->db2); std::swap(h->dc, h->dc2);
-  std::swap(h->dvW, h->dvW2); std::swap(h->dvb, h->dvb2); std::swap(h->dvc, h->dvc2);
+  h->dW.swap(h->dW2); h->db.swap(h->db2); h->dc.swap(h->dc2);
+  h->dvW.swap(h->dvW2); h->dvb.swap(h->dvb2); h->dvc.swap(h->dvc2);
   h->tables_dirty = false;
   h->params_version += 1;
 }
@@ -1031,7 +1016,7 @@ int launch_update(crbm_handle* h, int L_data) {
   fill_update_args(h, L_data, a);
   if (h->big()) {        // element-wise and in place: no table images to rebuild, no second buffer set
     UpdateArgs& u = a.u;
-    u.oW = h->dW; u.ob = h->db; u.oc = h->dc; u.ovW = h->dvW; u.ovb = h->dvb; u.ovc = h->dvc;
+    u.oW = h->dW.p; u.ob = h->db.p; u.oc = h->dc.p; u.ovW = h->dvW.p; u.ovb = h->dvb.p; u.ovc = h->dvc.p;
     hipLaunchKernelGGL(big_update_kernel, dim3(grid_for((long)h->KAM + h->K + h->A, 256, h->num_cu * 4)), dim3(256), 0, h->stream, u);
     HIPCHK(hipGetLastError());
     h->params_version += 1;
@@ -1062,13 +1047,13 @@ int launch_reduce_pair(crbm_handle* h, ReducePair pair, bool publish) {
   if (publish && h->ipc_on) {
     // this rank's slot of the step's parity in every rank's buffer, the own one as the base the others are offsets of
     const int parity = (int)(h->ipc_step & 1u);
-    float* base = ipc_slot_of(h->ipc_buf, h, parity, h->rank);
-    for (auto& half : pair.half) half.sums = base + (half.sums - h->d_sums);
+    float* base = ipc_slot_of(h->ipc_buf.p, h, parity, h->rank);
+    for (auto& half : pair.half) half.sums = base + (half.sums - h->d_sums.p);
     PublishTail t;
-    t.ticket = h->d_ticket; t.value = h->ipc_step + 1u;
+    t.ticket = h->d_ticket.p; t.value = h->ipc_step + 1u;
     t.push.n = h->nranks;
     for (int r = 0; r < IPC_MAX_RANKS; ++r) {
-      void* peer = r < h->nranks ? h->ipc_peer[r] : h->ipc_buf;
+      void* peer = r < h->nranks ? h->ipc_peer[r] : h->ipc_buf.p;
       t.push.delta[r] = (long long)(reinterpret_cast<char*>(ipc_slot_of(peer, h, parity, h->rank)) - reinterpret_cast<char*>(base));
       t.flag[r] = ipc_flag_of(peer, h, parity, h->rank);
     }
@@ -1108,7 +1093,7 @@ int train_local_dev(crbm_handle* h, const uint32_t* d_letters, int n, int L, boo
     rc = prepare_gibbs(h, g, h->cfg.cd_k, &pair.half[1], &t.g, &glds);
     if (rc) return rc;
     StatsLaunch d;
-    rc = prepare_stats(h, h->ms(), h->d_tables, h->partials, d_letters, n, L, true, g.threads, &t.d, &d);
+    rc = prepare_stats(h, h->ms(), h->d_tables.p, h->partials, d_letters, n, L, true, g.threads, &t.d, &d);
     if (rc) return rc;
     pair.half[0] = reduce_args(h, true, h->partials.p, d.grid, d.row, n);
     const unsigned lds = std::max(glds, (unsigned)d.lds);
@@ -1138,7 +1123,7 @@ int train_local_dev(crbm_handle* h, const uint32_t* d_letters, int n, int L, boo
     if (rc) return rc;
     rc = join_parts(h);      // (a partitioned chain launch: the statistics read what all partitions leave)
     if (rc) return rc;
-    rc = launch_stats(h, h->d_vf, h->B, h->Lv, false, sm, paired ? &pair.half[1] : nullptr);
+    rc = launch_stats(h, h->d_vf.p, h->B, h->Lv, false, sm, paired ? &pair.half[1] : nullptr);
     if (rc) return rc;
   }
   if (h->overlap) HIPCHK(hipEventRecord(h->ev_join, h->stream2));
@@ -1150,7 +1135,7 @@ int train_local_dev(crbm_handle* h, const uint32_t* d_letters, int n, int L, boo
       if (rc) return rc;
     }
   } else {   // a rank may own no rows of a short last mini-batch: contribute zeros
-    HIPCHK(hipMemsetAsync(h->d_sums + h->sl.data_off, 0, (size_t)(h->sl.n_d + 1 - h->sl.data_off) * sizeof(float), h->stream));
+    HIPCHK(hipMemsetAsync(h->d_sums.p + h->sl.data_off, 0, (size_t)(h->sl.n_d + 1 - h->sl.data_off) * sizeof(float), h->stream));
   }
   if (h->overlap) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
   return CRBM_OK;
@@ -1171,21 +1156,22 @@ uint32_t* ipc_status_of(void* base, const crbm_handle* h) {
 }
 
 int ipc_allocate(crbm_handle* h) {
-  if (h->ipc_buf) return CRBM_OK;
+  if (h->ipc_buf.p) return CRBM_OK;
   h->ipc_stride = (h->sl.count + 31) & ~31;
   // fine-grained device memory: coherent between agents, so a peer's system-scope stores are what this GPU's
   // system-scope loads see.  Plain (coarse-grained) device memory may keep stale lines of the rank's own buffer in
   // L2 after a peer's write over xGMI: refused unless CRBM_IPC_COARSE_OK=1 asks for it (one-GPU experiments).
-  void* p = nullptr;
-  const hipError_t fe = hipExtMallocWithFlags(&p, ipc_bytes(h), hipDeviceMallocFinegrained);
+  DevBuf<float> buf;                   // the handle's once it is zeroed
+  const size_t floats = ipc_bytes(h) / sizeof(float);
+  const hipError_t fe = buf.alloc(floats, true);
   if (fe != hipSuccess) {
     (void)hipGetLastError();
     if (env_int("CRBM_IPC_COARSE_OK", 0) == 0)
       return fail(h, CRBM_ERR_HIP, std::string("hipExtMallocWithFlags(hipDeviceMallocFinegrained) for the mapped sums buffer: ") + hipGetErrorString(fe));
-    HIPCHK(hipMalloc(&p, ipc_bytes(h)));
+    HIPCHK(buf.alloc(floats));
   }
-  HIPCHK(hipMemset(p, 0, ipc_bytes(h)));
-  h->ipc_buf = static_cast<float*>(p);
+  HIPCHK(hipMemset(buf.p, 0, ipc_bytes(h)));
+  h->ipc_buf = std::move(buf);
   return CRBM_OK;
 }
 
@@ -1197,9 +1183,9 @@ int launch_ipc_allreduce_update(crbm_handle* h, int L_data) {
     // the sums of this step were formed in d_sums (separate reductions of the two halves, or a rank without data
     // rows): push them and raise the flags in a launch of its own
     PublishArgs pa;
-    pa.src = h->d_sums; pa.value = value; pa.count = h->sl.count; pa.n = h->nranks;
+    pa.src = h->d_sums.p; pa.value = value; pa.count = h->sl.count; pa.n = h->nranks;
     for (int r = 0; r < IPC_MAX_RANKS; ++r) {
-      void* peer = r < h->nranks ? h->ipc_peer[r] : h->ipc_buf;
+      void* peer = r < h->nranks ? h->ipc_peer[r] : h->ipc_buf.p;
       pa.dst[r] = ipc_slot_of(peer, h, parity, h->rank);
       pa.flag[r] = ipc_flag_of(peer, h, parity, h->rank);
     }
@@ -1211,10 +1197,10 @@ int launch_ipc_allreduce_update(crbm_handle* h, int L_data) {
   fill_update_args(h, L_data, a.ut);
   for (int r = 0; r < IPC_MAX_RANKS; ++r) {            // everything the update reads is in this rank's own buffer
     const int src = r < h->nranks ? r : 0;
-    a.ipc.sums[r] = ipc_slot_of(h->ipc_buf, h, parity, src);
-    a.ipc.flags[r] = ipc_flag_of(h->ipc_buf, h, parity, src);
+    a.ipc.sums[r] = ipc_slot_of(h->ipc_buf.p, h, parity, src);
+    a.ipc.flags[r] = ipc_flag_of(h->ipc_buf.p, h, parity, src);
   }
-  a.ipc.status = ipc_status_of(h->ipc_buf, h);
+  a.ipc.status = ipc_status_of(h->ipc_buf.p, h);
   a.ipc.expect = value; a.ipc.nranks = h->nranks; a.ipc.count = h->sl.count;
   a.ipc.timeout_ticks = h->ipc_timeout_ticks;
   const unsigned grid = (unsigned)std::max(1, std::min((h->ms().TABLES_ALL + 4095) / 4096, 32));
@@ -1231,7 +1217,7 @@ int train_core(crbm_handle* h, const uint32_t* d_letters, int n, int L) {
   if (rc) return rc;
   if (h->ipc_on) return launch_ipc_allreduce_update(h, L);
   if (h->comm) {
-    ncclResult_t r = g_rccl.AllReduce(h->d_sums, h->d_sums, (size_t)h->sl.count, ncclFloat, ncclSum, h->comm, h->stream);
+    ncclResult_t r = g_rccl.AllReduce(h->d_sums.p, h->d_sums.p, (size_t)h->sl.count, ncclFloat, ncclSum, h->comm, h->stream);
     if (r != ncclSuccess) return fail(h, CRBM_ERR_RCCL, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
   }
   return launch_update(h, L);
@@ -1240,9 +1226,9 @@ int train_core(crbm_handle* h, const uint32_t* d_letters, int n, int L) {
 // The status word of the mapped-buffer all-reduce, read at a point where the stream is idle anyway: a wait for a
 // peer that ran out (update_tables_ipc_body) is an error of every training entry point and of crbm_sync from then on.
 int ipc_check(crbm_handle* h) {
-  if (!h->ipc_on || !h->ipc_buf) return CRBM_OK;
+  if (!h->ipc_on || !h->ipc_buf.p) return CRBM_OK;
   uint32_t st = 0;
-  HIPCHK(hipMemcpy(&st, ipc_status_of(h->ipc_buf, h), sizeof(st), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&st, ipc_status_of(h->ipc_buf.p, h), sizeof(st), hipMemcpyDeviceToHost));
   if (st != 0)
     return fail(h, CRBM_ERR_IPC_TIMEOUT, "mapped-buffer all-reduce: waited " + std::to_string(env_int("CRBM_IPC_TIMEOUT_MS", 30000)) +
                 " ms in vain for a peer's statistic sums (a rank died or fell out of step); no update has been applied since, "
@@ -1316,7 +1302,7 @@ int encode_rows(crbm_handle* h, const RowSource& src, int start, int cnt, const 
     HIPCHK(set.stage->ensure(count));
     HIPCHK(hipMemcpyAsync(set.stage->p, src.onehot + (size_t)start * h->A * L, count * sizeof(float), hipMemcpyHostToDevice, set.st));
     EncodeArgs a;
-    a.v = set.stage->p; a.letters = dst; a.flags = h->d_flags;
+    a.v = set.stage->p; a.letters = dst; a.flags = h->d_flags.p;
     a.n = cnt; a.L = L; a.LW = LW; a.A = h->A;
     if (h->A == 4) hipLaunchKernelGGL(encode_onehot_kernel, grid, dim3(256), 0, set.st, a);
     else hipLaunchKernelGGL(encode_onehot_any_kernel, grid, dim3(256), 0, set.st, a);
@@ -1326,7 +1312,7 @@ int encode_rows(crbm_handle* h, const RowSource& src, int start, int cnt, const 
     HIPCHK(hipMemcpyAsync(set.stage->p, src.codes + (size_t)start * L, bytes, hipMemcpyHostToDevice, set.st));
     EncodeCodesArgs a;
     a.codes = reinterpret_cast<const unsigned char*>(set.stage->p);
-    a.letters = dst; a.flags = h->d_flags;
+    a.letters = dst; a.flags = h->d_flags.p;
     a.n = cnt; a.L = L; a.LW = LW; a.A = h->A;
     if (h->A == 4) hipLaunchKernelGGL(encode_codes_kernel, grid, dim3(256), 0, set.st, a);
     else hipLaunchKernelGGL(encode_codes_any_kernel, grid, dim3(256), 0, set.st, a);
@@ -1390,7 +1376,7 @@ int sweep_finish(crbm_handle* h, const RowSource& src) {
 void sweep_drain(crbm_handle* h) {
   (void)hipStreamSynchronize(h->stream2);
   (void)hipStreamSynchronize(h->stream);
-  (void)hipMemsetAsync(h->d_flags, 0, sizeof(uint32_t), h->stream);
+  (void)hipMemsetAsync(h->d_flags.p, 0, sizeof(uint32_t), h->stream);
   (void)hipStreamSynchronize(h->stream);
 }
 
@@ -1503,7 +1489,7 @@ struct StreamSweep {
   // what every stream kernel reads of a chunk encoded into `set`: the one place a ScanInput is filled
   ScanInput input(const SweepSet& set, int32_t starts, int32_t tiles) const {
     ScanInput a;
-    a.tables = h->big() ? h->d_slab_tables : h->d_tables;
+    a.tables = h->big() ? h->d_slab_tables.p : h->d_tables.p;
     a.letters = set.letters->p; a.valid = set.own->scan_valid.p;
     a.starts = starts; a.tiles = tiles; a.table_stride = kms->TABLES_ALL;
     if (h->big()) a.plan = slab_plan(h);
@@ -1514,20 +1500,12 @@ struct StreamSweep {
   template <class Stage, class Launch, class Collect>
   int run_chunks(int n, int slab, const char* timing_env, const char* unit, Stage stage, Launch launch, Collect collect) {
     const bool timing = env_int(timing_env, 0) != 0;
-    struct Events {                      // destroyed on every way out
-      hipEvent_t e[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-      ~Events() {
-        for (auto& set : e)
-          for (hipEvent_t ev : set)
-            if (ev) (void)hipEventDestroy(ev);
-      }
-    } events;
-    auto& tev = events.e;
+    Event tev[2][2];
     double device_ms = 0.0;
     int timed = 0;
     if (timing)
       for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) HIPCHK(hipEventCreate(&tev[i][j]));
+        for (int j = 0; j < 2; ++j) HIPCHK(tev[i][j].create());
     ScanInput in[2];
     Chunk chunk[2];
     const int rc = run_slabs(n, slab, 2,
@@ -1542,7 +1520,7 @@ struct StreamSweep {
         if (timing) HIPCHK(hipEventRecord(tev[si][0], set.st));
         ScanEncodeArgs e;
         e.codes = reinterpret_cast<const unsigned char*>(set.stage->p);
-        e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags;
+        e.letters = set.letters->p; e.valid = set.own->scan_valid.p; e.flags = h->d_flags.p;
         e.n = c.n; e.valid_words = l.valid_words;
         hipLaunchKernelGGL(scan_encode_kernel, dim3(grid_for(l.valid_words, 256, h->num_cu * 8)), dim3(256), 0, set.st, e);
         HIPCHK(hipGetLastError());
@@ -1570,10 +1548,10 @@ struct StreamSweep {
     HIPCHK(hipStreamSynchronize(h->stream2));
     HIPCHK(hipStreamSynchronize(h->stream));
     uint32_t flags = 0;
-    HIPCHK(hipMemcpyAsync(&flags, h->d_flags, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&flags, h->d_flags.p, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (flags) {
-      HIPCHK(hipMemsetAsync(h->d_flags, 0, sizeof(uint32_t), h->stream));
+      HIPCHK(hipMemsetAsync(h->d_flags.p, 0, sizeof(uint32_t), h->stream));
       HIPCHK(hipStreamSynchronize(h->stream));
       return fail(h, CRBM_ERR_INVALID, kBadStreamCode);
     }
@@ -1676,7 +1654,7 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
     return fail(h, CRBM_ERR_NO_GPU, "no HIP device visible (this library has no CPU path)");
   ARGCHK(cfg->device >= 0 && cfg->device < ndev, "device ordinal out of range");
 
-  crbm_handle* hh = new crbm_handle();
+  std::unique_ptr<crbm_handle> hh(new crbm_handle());      // deleted on every early return below
   hh->cfg = *cfg;
   hh->K = cfg->num_motifs; hh->M = cfg->motif_length; hh->ds = cfg->doublestranded ? 1 : 0;
   hh->A = cfg->input_dims;
@@ -1685,16 +1663,9 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
   hh->seed = cfg->seed;
   hh->device = cfg->device;
   hh->sl = sums_layout(hh->K, hh->M, hh->A);
-  auto bail = [&](int code) { crbm_destroy(hh); return code; };
-  hipError_t e;
-#define TRY(expr)                                                                                 \
-  if ((e = (expr)) != hipSuccess) {                                                               \
-    g_create_error = std::string(#expr) + ": " + hipGetErrorString(e);                            \
-    return bail(CRBM_ERR_HIP);                                                                    \
-  }
-  TRY(hipSetDevice(hh->device));
+  HIPCHK(hipSetDevice(hh->device));
   hipDeviceProp_t prop;
-  TRY(hipGetDeviceProperties(&prop, hh->device));
+  HIPCHK(hipGetDeviceProperties(&prop, hh->device));
   hh->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   {
     int khz = 0;      // ticks of the GPU's constant-rate clock (s_memrealtime) per millisecond
@@ -1705,10 +1676,7 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
   hh->plan = plan_launches(hh->K, hh->M, hh->ds, hh->A, cfg->pooling, hh->Lf, hh->B, hh->num_cu);
   const LaunchPlan& plan = hh->plan;
   hh->NW = plan.ms.NW;
-  if (plan.refusal) {
-    g_create_error = plan.refusal;
-    return bail(CRBM_ERR_INVALID);
-  }
+  if (plan.refusal) return fail(h, CRBM_ERR_INVALID, plan.refusal);
   // (generic models: no specialised kernels, no table images; the state layout is the same -- K-bit masks, 2-bit letters)
   hh->LWs = hh->big() ? letter_words_any(hh->A, hh->Lv) : plan.chain[1].gl.LWs;
   hh->variant = 1; hh->topdown_mode = 2;
@@ -1720,38 +1688,31 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
     hh->topdown_mode = (td && !strcmp(td, "dense") && plan.has_dense) ? 1 : 2;
     hh->variant = hh->topdown_mode == 1 ? 0 : 1;
     std::string err;
-    if (jit_load(hh->K, hh->M, hh->ds, plan.G, plan.GS, hh->ms().POOL, plan.gibbs_wpe, plan.gibbs_tb, &hh->jk, &err) != 0) {
-      g_create_error = "kernel specialisation failed: " + err;
-      return bail(CRBM_ERR_HIP);
-    }
+    if (jit_load(hh->K, hh->M, hh->ds, plan.G, plan.GS, hh->ms().POOL, plan.gibbs_wpe, plan.gibbs_tb, &hh->jk, &err) != 0)
+      return fail(h, CRBM_ERR_HIP, "kernel specialisation failed: " + err);
     // (only the set-bit walk has them: a handle pinned to the dense variant never consults jg and does not pay for it)
     if (hh->variant == 1 &&
-        jit_load_geo(hh->K, hh->M, hh->ds, hh->ms().POOL, plan.gibbs_wpe, jit_geo(plan.geo_plain, hh->Lf), jit_geo(plan.geo_fused, hh->Lf), &hh->jg, &err) != 0) {
-      g_create_error = "kernel specialisation (launch geometry) failed: " + err;
-      return bail(CRBM_ERR_HIP);
-    }
+        jit_load_geo(hh->K, hh->M, hh->ds, hh->ms().POOL, plan.gibbs_wpe, jit_geo(plan.geo_plain, hh->Lf), jit_geo(plan.geo_fused, hh->Lf), &hh->jg, &err) != 0)
+      return fail(h, CRBM_ERR_HIP, "kernel specialisation (launch geometry) failed: " + err);
   }
-  TRY(hipStreamCreateWithFlags(&hh->stream, hipStreamNonBlocking));
-  TRY(hipStreamCreateWithFlags(&hh->stream2, hipStreamNonBlocking));
-  TRY(hipEventCreate(&hh->ev0));
-  TRY(hipEventCreate(&hh->ev1));
-  TRY(hipEventCreateWithFlags(&hh->ev_fork, hipEventDisableTiming));
-  TRY(hipEventCreateWithFlags(&hh->ev_join, hipEventDisableTiming));
+  HIPCHK(hh->stream.create());
+  HIPCHK(hh->stream2.create());
+  HIPCHK(hh->ev0.create());
+  HIPCHK(hh->ev1.create());
+  HIPCHK(hh->ev_fork.create_untimed());
+  HIPCHK(hh->ev_join.create_untimed());
   if (plan.chain_parts > 1) {
-    TRY(hipEventCreateWithFlags(&hh->ev_parts_fork, hipEventDisableTiming));
-    TRY(hipEventCreate(&hh->ev_cal0));
-    TRY(hipEventCreate(&hh->ev_cal1));
-    hh->part_stream[0] = hh->stream;          // partition 0 rides on the handle's own stream: one hardware queue fewer
-    for (int p = 1; p < plan.chain_parts; ++p) {
-      TRY(hipStreamCreateWithFlags(&hh->part_stream[p], hipStreamNonBlocking));
-      TRY(hipEventCreate(&hh->part_done[p]));     // with timestamps: crbm_time_gibbs reads them
-      {
-        PartWorker* w = new PartWorker();
-        w->device = hh->device;
-        w->stream = hh->part_stream[p];
-        w->th = std::thread(part_worker_main, w);
-        hh->part_worker[p] = w;
-      }
+    HIPCHK(hh->ev_parts_fork.create_untimed());
+    HIPCHK(hh->ev_cal0.create());
+    HIPCHK(hh->ev_cal1.create());
+    for (int p = 1; p < plan.chain_parts; ++p) {      // (partition 0 rides on the handle's own stream: one hardware queue fewer)
+      Partition& part = hh->part[p];
+      HIPCHK(part.stream.create());
+      HIPCHK(part.done.create());                // with timestamps: crbm_time_gibbs reads them
+      part.worker.reset(new PartWorker());
+      part.worker->device = hh->device;
+      part.worker->stream = part.stream;
+      part.worker->th = std::thread(part_worker_main, part.worker.get());
     }
   }
   hh->overlap = env_int("CRBM_OVERLAP", 0) != 0;   // measured: no gain once the statistics kernel fills the chip
@@ -1759,40 +1720,36 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
   //  starts on a multiple of ten and may reach past the model's end, slab_origin)
   const size_t pad_k = hh->big() ? 10 : 0;
   const size_t kam = (size_t)hh->KAM + pad_k * hh->A * hh->M, k = (size_t)hh->K + pad_k;
-  TRY(hipMalloc((void**)&hh->dW, kam * 4)); TRY(hipMalloc((void**)&hh->dvW, kam * 4));
-  TRY(hipMalloc((void**)&hh->db, k * 4));   TRY(hipMalloc((void**)&hh->dvb, k * 4));
-  const size_t cb = (size_t)std::max(4, hh->A) * 4;
-  TRY(hipMalloc((void**)&hh->dc, cb));      TRY(hipMalloc((void**)&hh->dvc, cb));
-  TRY(hipMemset(hh->dW, 0, kam * 4)); TRY(hipMemset(hh->dvW, 0, kam * 4));
-  TRY(hipMemset(hh->db, 0, k * 4));   TRY(hipMemset(hh->dvb, 0, k * 4));
-  TRY(hipMemset(hh->dc, 0, cb));      TRY(hipMemset(hh->dvc, 0, cb));
-  TRY(hipMalloc((void**)&hh->dW2, kam * 4)); TRY(hipMalloc((void**)&hh->dvW2, kam * 4));
-  TRY(hipMalloc((void**)&hh->db2, k * 4));   TRY(hipMalloc((void**)&hh->dvb2, k * 4));
-  TRY(hipMalloc((void**)&hh->dc2, cb));      TRY(hipMalloc((void**)&hh->dvc2, cb));
-  TRY(hipMalloc((void**)&hh->d_tables, hh->big() ? 64 : (size_t)hh->ms().TABLES_ALL * 4));
-  if (plan.GS != plan.G) TRY(hipMalloc((void**)&hh->d_tf_solo, (size_t)plan.ms_solo.TAB * 4));
+  const size_t cb = (size_t)std::max(4, hh->A);
+  HIPCHK(hh->dW.alloc_zeroed(kam)); HIPCHK(hh->dvW.alloc_zeroed(kam));
+  HIPCHK(hh->db.alloc_zeroed(k));   HIPCHK(hh->dvb.alloc_zeroed(k));
+  HIPCHK(hh->dc.alloc_zeroed(cb));  HIPCHK(hh->dvc.alloc_zeroed(cb));
+  HIPCHK(hh->dW2.alloc(kam)); HIPCHK(hh->dvW2.alloc(kam));
+  HIPCHK(hh->db2.alloc(k));   HIPCHK(hh->dvb2.alloc(k));
+  HIPCHK(hh->dc2.alloc(cb));  HIPCHK(hh->dvc2.alloc(cb));
+  HIPCHK(hh->d_tables.alloc(hh->big() ? 16 : (size_t)hh->ms().TABLES_ALL));
+  if (plan.GS != plan.G) HIPCHK(hh->d_tf_solo.alloc((size_t)plan.ms_solo.TAB));
   const size_t mwords = (size_t)hh->B * hh->Lf * hh->NW;
-  TRY(hipMalloc((void**)&hh->d_hm, mwords * 4)); TRY(hipMemset(hh->d_hm, 0, mwords * 4));
-  TRY(hipMalloc((void**)&hh->d_hmp, mwords * 4)); TRY(hipMemset(hh->d_hmp, 0, mwords * 4));
+  HIPCHK(hh->d_hm.alloc_zeroed(mwords));
+  HIPCHK(hh->d_hmp.alloc_zeroed(mwords));
   const size_t vwords = (size_t)hh->B * hh->LWs;
-  TRY(hipMalloc((void**)&hh->d_vf, vwords * 4)); TRY(hipMemset(hh->d_vf, 0, vwords * 4));
-  TRY(hipMalloc((void**)&hh->d_flags, 16)); TRY(hipMemset(hh->d_flags, 0, 16));
-  TRY(hipMalloc((void**)&hh->d_ones, 16)); TRY(hipMemset(hh->d_ones, 0, 16));
+  HIPCHK(hh->d_vf.alloc_zeroed(vwords));
+  HIPCHK(hh->d_flags.alloc_zeroed(4));
+  HIPCHK(hh->d_ones.alloc_zeroed(2));
   {
     // one slot per wave of the largest launch; a partitioned launch is chain_parts launches of the partition's geometry
     size_t slots = plan.part.on() ? (size_t)plan.chain_parts * plan.part.grid * (plan.part.threads / 64) : 0;
     for (const ChainGeom* g : {&plan.chain[0], &plan.chain[1], &plan.solo})
       if (g->on()) slots = std::max(slots, (size_t)g->grid * (g->threads / 64));
     slots += 64;
-    TRY(hipMalloc((void**)&hh->d_nset, slots * 4)); TRY(hipMemset(hh->d_nset, 0, slots * 4));
+    HIPCHK(hh->d_nset.alloc_zeroed(slots));
   }
-  TRY(hipMalloc((void**)&hh->d_sums, (size_t)hh->sl.count * 4)); TRY(hipMemset(hh->d_sums, 0, (size_t)hh->sl.count * 4));
-  TRY(hipMalloc((void**)&hh->d_ticket, 16)); TRY(hipMemset(hh->d_ticket, 0, 16));
-  TRY(hipMalloc((void**)&hh->d_probe, 32)); TRY(hipMemset(hh->d_probe, 0, 32));
+  HIPCHK(hh->d_sums.alloc_zeroed((size_t)hh->sl.count));
+  HIPCHK(hh->d_ticket.alloc_zeroed(4));
+  HIPCHK(hh->d_probe.alloc_zeroed(4));
   // the memsets above go out on the null stream, which the handle's non-blocking streams do not wait for: without this
   // a zeroing of W, b, c could land after the crbm_set_params that follows (seen: a generic model evaluated with W = 0)
-  TRY(hipDeviceSynchronize());
-#undef TRY
+  HIPCHK(hipDeviceSynchronize());
   hh->tables_dirty = true;
   {
     const char* sv = getenv("CRBM_STATS");
@@ -1806,59 +1763,19 @@ int crbm_create(const crbm_config* cfg, crbm_handle** out) {
     }
   }
   hh->stats_rows = env_int("CRBM_STATS_ROWS", 0);   // 0: one resident wave of blocks
-  slab_setup(hh);                                   // generic DNA models: their statistics on the matrix cores, slab by slab
-  *out = hh;
+  slab_setup(hh.get());                             // generic DNA models: their statistics on the matrix cores, slab by slab
+  *out = hh.release();
   return CRBM_OK;
 }
 
 int crbm_destroy(crbm_handle* h) {
   if (!h) return CRBM_OK;
   (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-  for (int p = 0; p < 4; ++p) {
-    if (PartWorker* w = h->part_worker[p]) {
-      {
-        std::lock_guard<std::mutex> lock(w->mu);
-        w->stop = true;
-      }
-      w->cv.notify_one();
-      if (w->th.joinable()) w->th.join();
-      delete w;
-      h->part_worker[p] = nullptr;
-    }
-    if (p > 0 && h->part_stream[p]) { (void)hipStreamSynchronize(h->part_stream[p]); (void)hipStreamDestroy(h->part_stream[p]); }
-    if (h->part_done[p]) (void)hipEventDestroy(h->part_done[p]);
+  if (h->comm && g_rccl.CommDestroy) {
+    (void)hipStreamSynchronize(h->stream);      // the collectives of the communicator ran on it
+    g_rccl.CommDestroy(h->comm);
   }
-  if (h->ev_parts_fork) (void)hipEventDestroy(h->ev_parts_fork);
-  if (h->ev_cal0) (void)hipEventDestroy(h->ev_cal0);
-  if (h->ev_cal1) (void)hipEventDestroy(h->ev_cal1);
-  if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
-  for (int r = 0; r < IPC_MAX_RANKS; ++r)
-    if (h->ipc_peer[r] && h->ipc_peer[r] != h->ipc_buf) (void)hipIpcCloseMemHandle(h->ipc_peer[r]);
-  if (h->ipc_buf) (void)hipFree(h->ipc_buf);
-  slab_destroy(h);
-  void* ptrs[] = {h->dW2, h->db2, h->dc2, h->dvW2, h->dvb2, h->dvc2, h->dW, h->db, h->dc, h->dvW, h->dvb, h->dvc, h->d_hm, h->d_hmp, h->d_vf, h->d_flags, h->d_ones, h->d_nset, h->d_sums, h->d_ticket, h->d_tables, h->d_tf_solo, h->d_probe, h->d_timeline};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  h->stage.release(); h->stage2.release(); h->out_a.release(); h->out_b.release(); h->out_c.release();
-  h->letters.release(); h->letters2.release(); h->masks_tmp.release(); h->out_a2.release(); h->out_b2.release();
-  for (auto& d : h->dataset) d.release(); h->partials.release(); h->partials2.release();
-  for (auto& b : h->set_bufs) {
-    b.site_recs.release(); b.site_count.release(); b.site_keys.release();
-    b.scan_valid.release(); b.scan_off.release(); b.scan_lanes.release(); b.scan_tiles.release();
-    b.mut_df.release(); b.mut_pll.release(); b.mut_rows.release(); b.var_windows.release();
-  }
-  h->ais_betas.release(); h->ais_base.release(); h->ais_logw.release(); h->ais_state.release(); h->hist.release(); h->rec_acc.release(); h->rec_start.release();
-  if (h->jk.module) (void)hipModuleUnload(h->jk.module);
-  if (h->jg.module) (void)hipModuleUnload(h->jg.module);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->stream2) (void)hipStreamDestroy(h->stream2);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;      // every member releases what it owns, in the order the struct states
   return CRBM_OK;
 }
 
@@ -1878,9 +1795,9 @@ int crbm_destroy(crbm_handle* h) {
 int crbm_set_params(crbm_handle* h, const float* W, const float* b, const float* c) {
   ENTER();
   ARGCHK(W && b && c, "null argument");
-  HIPCHK(hipMemcpyAsync(h->dW, W, (size_t)h->KAM * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->db, b, (size_t)h->K * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->dc, c, (size_t)h->A * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->dW.p, W, (size_t)h->KAM * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->db.p, b, (size_t)h->K * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->dc.p, c, (size_t)h->A * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->tables_dirty = true;
   h->params_version += 1;
@@ -1890,9 +1807,9 @@ int crbm_set_params(crbm_handle* h, const float* W, const float* b, const float*
 int crbm_get_params(crbm_handle* h, float* W, float* b, float* c) {
   ENTER();
   ARGCHK(W && b && c, "null argument");
-  HIPCHK(hipMemcpyAsync(W, h->dW, (size_t)h->KAM * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(b, h->db, (size_t)h->K * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(c, h->dc, (size_t)h->A * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(W, h->dW.p, (size_t)h->KAM * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(b, h->db.p, (size_t)h->K * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(c, h->dc.p, (size_t)h->A * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return CRBM_OK;
 }
@@ -1900,9 +1817,9 @@ int crbm_get_params(crbm_handle* h, float* W, float* b, float* c) {
 int crbm_set_velocities(crbm_handle* h, const float* vW, const float* vb, const float* vc) {
   ENTER();
   ARGCHK(vW && vb && vc, "null argument");
-  HIPCHK(hipMemcpyAsync(h->dvW, vW, (size_t)h->KAM * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->dvb, vb, (size_t)h->K * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->dvc, vc, (size_t)h->A * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->dvW.p, vW, (size_t)h->KAM * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->dvb.p, vb, (size_t)h->K * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->dvc.p, vc, (size_t)h->A * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return CRBM_OK;
 }
@@ -1910,9 +1827,9 @@ int crbm_set_velocities(crbm_handle* h, const float* vW, const float* vb, const 
 int crbm_get_velocities(crbm_handle* h, float* vW, float* vb, float* vc) {
   ENTER();
   ARGCHK(vW && vb && vc, "null argument");
-  HIPCHK(hipMemcpyAsync(vW, h->dvW, (size_t)h->KAM * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(vb, h->dvb, (size_t)h->K * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(vc, h->dvc, (size_t)h->A * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(vW, h->dvW.p, (size_t)h->KAM * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(vb, h->dvb.p, (size_t)h->K * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(vc, h->dvc.p, (size_t)h->A * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return CRBM_OK;
 }
@@ -1924,11 +1841,11 @@ int crbm_set_fantasy(crbm_handle* h, const float* hid, const float* hid_prime) {
   const size_t count = (size_t)h->B * h->K * h->Lf;
   HIPCHK(h->stage.ensure(count));
   const float* src[2] = {hid, hid_prime};
-  uint32_t* dst[2] = {h->d_hm, h->d_hmp};
+  uint32_t* dst[2] = {h->d_hm.p, h->d_hmp.p};
   for (int sidx = 0; sidx < 1 + h->ds; ++sidx) {
     HIPCHK(hipMemcpyAsync(h->stage.p, src[sidx], count * 4, hipMemcpyHostToDevice, h->stream));
     HiddenPackArgs a;
-    a.dense = h->stage.p; a.masks = dst[sidx]; a.flags = h->d_flags;
+    a.dense = h->stage.p; a.masks = dst[sidx]; a.flags = h->d_flags.p;
     a.n = h->B; a.K = h->K; a.Lh = h->Lf; a.NW = h->NW;
     hipLaunchKernelGGL(pack_hidden_kernel, dim3(grid_for((long)h->B * h->Lf, 256, h->num_cu * 8)), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
@@ -1943,11 +1860,11 @@ int crbm_get_fantasy(crbm_handle* h, float* hid, float* hid_prime) {
   const size_t count = (size_t)h->B * h->K * h->Lf;
   HIPCHK(h->stage.ensure(count));
   float* dsth[2] = {hid, hid_prime};
-  uint32_t* src[2] = {h->d_hm, h->d_hmp};
+  uint32_t* src[2] = {h->d_hm.p, h->d_hmp.p};
   for (int sidx = 0; sidx < 1 + h->ds; ++sidx) {
     if (!dsth[sidx]) continue;
     HiddenPackArgs a;
-    a.dense = h->stage.p; a.masks = src[sidx]; a.flags = h->d_flags;
+    a.dense = h->stage.p; a.masks = src[sidx]; a.flags = h->d_flags.p;
     a.n = h->B; a.K = h->K; a.Lh = h->Lf; a.NW = h->NW;
     hipLaunchKernelGGL(unpack_hidden_kernel, dim3(grid_for((long)h->B * h->Lf, 256, h->num_cu * 8)), dim3(256), 0, h->stream, a);
     HIPCHK(hipGetLastError());
@@ -1963,7 +1880,7 @@ int crbm_get_fantasy_visible(crbm_handle* h, float* v) {
   const size_t count = (size_t)h->B * h->A * h->Lv;
   HIPCHK(h->stage.ensure(count));
   DecodeArgs a;
-  a.letters = h->d_vf; a.v = h->stage.p; a.n = h->B; a.L = h->Lv; a.LW = h->LWs; a.A = h->A;
+  a.letters = h->d_vf.p; a.v = h->stage.p; a.n = h->B; a.L = h->Lv; a.LW = h->LWs; a.A = h->A;
   if (h->A == 4) hipLaunchKernelGGL(decode_onehot_kernel, dim3(grid_for((long)h->B * h->Lv, 256, h->num_cu * 8)), dim3(256), 0, h->stream, a);
   else hipLaunchKernelGGL(decode_onehot_any_kernel, dim3(grid_for((long)h->B * h->Lv, 256, h->num_cu * 8)), dim3(256), 0, h->stream, a);
   HIPCHK(hipGetLastError());
@@ -2169,25 +2086,17 @@ int crbm_time_gibbs(crbm_handle* h, int32_t k, int32_t launches, float* total_ms
   const bool want_timeline = env_int("CRBM_GIBBS_TIMELINE", 0) != 0 && launches <= 4096;
   if (want_timeline) {
     const int need = launches * std::max(1, h->plan.chain_parts);
-    if (need > h->timeline_cap) {
-      if (h->d_timeline) (void)hipFree(h->d_timeline);
-      h->d_timeline = nullptr;
-      HIPCHK(hipMalloc((void**)&h->d_timeline, (size_t)need * 16));
-      h->timeline_cap = need;
-    }
-    HIPCHK(hipMemset(h->d_timeline, 0, (size_t)h->timeline_cap * 16));
+    if (need > h->timeline_cap()) HIPCHK(h->d_timeline.alloc((size_t)need * 2));
+    HIPCHK(hipMemset(h->d_timeline.p, 0, (size_t)h->timeline_cap() * 16));
     h->timeline_next = 0;
-  } else {
-    h->timeline_cap = h->d_timeline ? h->timeline_cap : 0;
-    h->timeline_next = h->timeline_cap;      // no slots handed out
-  }
+  } else h->timeline_next = h->timeline_cap();      // no slots handed out
   struct TimelineDump {
     crbm_handle* h; bool on;
     ~TimelineDump() {
-      if (!on || !h->d_timeline) return;
+      if (!on || !h->d_timeline.p) return;
       (void)hipDeviceSynchronize();
       std::vector<unsigned long long> t((size_t)h->timeline_next * 2);
-      if (hipMemcpy(t.data(), h->d_timeline, t.size() * 8, hipMemcpyDeviceToHost) != hipSuccess || t.empty()) return;
+      if (hipMemcpy(t.data(), h->d_timeline.p, t.size() * 8, hipMemcpyDeviceToHost) != hipSuccess || t.empty()) return;
       unsigned long long t0 = ~0ull;
       for (size_t i = 0; i < t.size(); i += 2) if (t[i]) t0 = std::min(t0, t[i]);
       const double us = 1000.0 / h->wall_khz;
@@ -2197,7 +2106,7 @@ int crbm_time_gibbs(crbm_handle* h, int32_t k, int32_t launches, float* total_ms
         fprintf(stderr, " %.1f-%.1f", (t[i] - t0) * us, (t[i + 1] - t0) * us);
       }
       fprintf(stderr, "\n");
-      h->timeline_next = h->timeline_cap;
+      h->timeline_next = h->timeline_cap();
     }
   } timeline_dump{h, want_timeline};
   struct ProbeOff { crbm_handle* h; ~ProbeOff() { h->probe_on = false; } } probe_off{h};
@@ -2229,13 +2138,13 @@ int crbm_time_gibbs(crbm_handle* h, int32_t k, int32_t launches, float* total_ms
       if (rc) return rc;
     }
     HIPCHK(hipEventRecord(h->ev1, h->stream));                       // partition 0 = the main stream
-    for (int p = 1; p < h->plan.chain_parts; ++p) HIPCHK(hipEventRecord(h->part_done[p], h->part_stream[p]));
+    for (int p = 1; p < h->plan.chain_parts; ++p) HIPCHK(hipEventRecord(h->part[p].done, h->part[p].stream));
     HIPCHK(spin_until(h->ev1));
     HIPCHK(hipEventElapsedTime(&worst, h->ev0, h->ev1));
     for (int p = 1; p < h->plan.chain_parts; ++p) {
       float ms = 0.f;
-      HIPCHK(spin_until(h->part_done[p]));
-      HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->part_done[p]));
+      HIPCHK(spin_until(h->part[p].done));
+      HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->part[p].done));
       worst = std::max(worst, ms);
     }
     *total_ms = worst;
@@ -2307,7 +2216,7 @@ int crbm_v_given_h(crbm_handle* h, const float* hid, const float* hid_prime, int
   if (prob) HIPCHK(h->out_b.ensure(vcount));
   if (sample) HIPCHK(h->out_c.ensure(vcount));
   VghArgs a;
-  a.W = h->dW; a.c = h->dc; a.K = h->K; a.M = h->M;
+  a.W = h->dW.p; a.c = h->dc.p; a.K = h->K; a.M = h->M;
   a.hid = h->stage.p; a.hidp = hid_prime ? h->stage2.p : nullptr;
   a.n = n; a.Lh = Lh; a.L = L;
   a.TS = tile_seqs(L, 4096);
@@ -2380,7 +2289,7 @@ int launch_free_energy(crbm_handle* h, const uint32_t* rows, int n, int L, const
   HIPCHK(set.ob->ensure((size_t)n * h->K));
   if (h->big()) return big_launch_eval(h, rows, n, L, 0, set.oa->p, set.ob->p, nullptr, nullptr, nullptr, set.fe_scratch, set.st);
   FeArgs a;
-  a.tables = h->d_tables;
+  a.tables = h->d_tables.p;
   a.letters = rows;
   a.n = n; a.L = L; a.Lh = L - h->M + 1; a.LW = lw(h, L);
   a.fe = set.oa->p; a.fem = set.ob->p;
@@ -2418,12 +2327,12 @@ int eval_data_any(crbm_handle* h, const RowSource& src, float* mfe, float* nmh) 
   const int slab = slab_rows(n, src.in_bytes_per_row() + ((size_t)h->K + 1) * sizeof(float));
   std::vector<float> fe((size_t)slab);
   double tot = 0.0;
-  HIPCHK(hipMemsetAsync(h->d_ones, 0, sizeof(unsigned long long), h->stream));
+  HIPCHK(hipMemsetAsync(h->d_ones.p, 0, sizeof(unsigned long long), h->stream));
   rc = sweep_run(h, src, slab, 1,
     [&](const SweepSet& set, const uint32_t* rows, int start, int cnt) -> int {
       const int r = launch_free_energy(h, rows, cnt, L, set);
       // mean of a fresh forward-strand sample (convRBM.py:469-472); rows keep their index within the call
-      return r ? r : launch_hgv(h, rows, cnt, L, 0, nullptr, nullptr, nullptr, h->d_ones, KIND_EVAL_H, h->eval_step, (uint32_t)start);
+      return r ? r : launch_hgv(h, rows, cnt, L, 0, nullptr, nullptr, nullptr, h->d_ones.p, KIND_EVAL_H, h->eval_step, (uint32_t)start);
     },
     [&](const SweepSet& set, const uint32_t*, int, int cnt) -> int {
       HIPCHK(hipMemcpyAsync(fe.data(), set.oa->p, (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost, set.st));
@@ -2435,7 +2344,7 @@ int eval_data_any(crbm_handle* h, const RowSource& src, float* mfe, float* nmh) 
   *mfe = (float)(tot / n);                       // convRBM.py:636-638
   h->eval_step += 1;
   unsigned long long ones = 0;
-  HIPCHK(hipMemcpyAsync(&ones, h->d_ones, sizeof(ones), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&ones, h->d_ones.p, sizeof(ones), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   *nmh = (float)((double)ones / ((double)n * h->K * (L - h->M + 1)));
   return CRBM_OK;
@@ -2476,7 +2385,7 @@ int hit_summary_any(crbm_handle* h, const RowSource& src, float* hmax, float* hm
         HIPCHK(hipMemsetAsync(set.ob->p, 0, (size_t)cnt * K * 8, set.st));
       }
       HitArgs a;
-      a.tables = h->d_tables; a.letters = rows;
+      a.tables = h->d_tables.p; a.letters = rows;
       a.n = cnt; a.L = L; a.Lh = Lh; a.LW = lw(h, L);
       a.hmax = hmax ? set.oa->p : nullptr;
       a.hsum = (hmean && nchunks == 1) ? set.ob->p : nullptr;
@@ -2594,7 +2503,7 @@ int motif_sites_any(crbm_handle* h, const RowSource& src, float threshold, int64
     }
     if (want_best && nchunks > 1) HIPCHK(hipMemsetAsync(o.best, 0, (size_t)cnt * K * 8, set.st));   // (atomicMax across chunks)
     SitesArgs a;
-    a.tables = h->d_tables; a.letters = rows;
+    a.tables = h->d_tables.p; a.letters = rows;
     a.n = cnt; a.L = L; a.Lh = Lh; a.LW = lw(h, L);
     a.o = o;
     const unsigned gx = (unsigned)std::max(1, std::min((cnt + 3) / 4, std::max(1, h->num_cu * 8 / nchunks)));
@@ -2830,9 +2739,9 @@ int scan_records_any(crbm_handle* h, const uint8_t* codes, int64_t T, const int6
   if (rc) return rc;
   std::vector<float> W((size_t)K * 4 * M), b((size_t)K);
   float c[4];
-  HIPCHK(hipMemcpyAsync(W.data(), h->dW, W.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(b.data(), h->db, b.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(c, h->dc, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(W.data(), h->dW.p, W.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(b.data(), h->db.p, b.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(c, h->dc.p, sizeof(c), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   const int e = records_unit_exp(records_x_max(W.data(), b.data(), K, M), sw.S);
   if (unit) *unit = records_unit(e);
@@ -2947,7 +2856,7 @@ int variant_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t
       HIPCHK(jit_launch(sw.kjk->variant_effects, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(*sw.kms), set.st));
       if (dfe) {
         VariantCombineArgs c;
-        c.per_motif = set.oa->p; c.codes = staged; c.alt = a.alt; c.c = h->dc; c.dfe = set.ob->p;
+        c.per_motif = set.oa->p; c.codes = staged; c.alt = a.alt; c.c = h->dc.p; c.dfe = set.ob->p;
         c.cnt = cnt; c.K = K; c.CW = CW; c.M = M;
         hipLaunchKernelGGL(variant_combine_kernel, dim3(grid_for(cnt, 256, h->num_cu * 8)), dim3(256), 0, set.st, c);
         HIPCHK(hipGetLastError());
@@ -3044,7 +2953,7 @@ int allele_effects_any(crbm_handle* h, const uint8_t* codes, int64_t T, int64_t 
       HIPCHK(jit_launch(sw.kjk->allele_effects, a, gx, (unsigned)nslab, 256, (unsigned)tab_bytes(*sw.kms), set.st));
       if (dfe) {
         AlleleCombineArgs c;
-        c.per_motif = set.oa->p; c.codes = staged; c.table = a.table; c.c = h->dc; c.dfe = set.ob->p;
+        c.per_motif = set.oa->p; c.codes = staged; c.table = a.table; c.c = h->dc.p; c.dfe = set.ob->p;
         c.cnt = cnt; c.K = K; c.M = M; c.pad_ = 0;
         hipLaunchKernelGGL(allele_combine_kernel, dim3(grid_for(cnt, 256, h->num_cu * 8)), dim3(256), 0, set.st, c);
         HIPCHK(hipGetLastError());
@@ -3112,7 +3021,7 @@ int mutagenesis_any(crbm_handle* h, const RowSource& src, float* dfe, float* pll
       float* d_pll = set.own->mut_pll.p;
       if (fused) {
         MutArgs a;
-        a.tables = h->d_tables; a.letters = rows;
+        a.tables = h->d_tables.p; a.letters = rows;
         a.n = cnt; a.L = L; a.Lh = L - h->M + 1; a.LW = LW;
         a.dfe = d_df; a.pll = d_pll;
         // num_cu * 8 blocks like the other sweep kernels; a grid of only the resident blocks (5 per CU at config #2: no
@@ -3130,7 +3039,7 @@ int mutagenesis_any(crbm_handle* h, const RowSource& src, float* dfe, float* pll
       const int r = launch_free_energy(h, e.out, (int)R, L, set);
       if (r) return r;
       MutCombineArgs c;
-      c.fem = set.ob->p; c.c = h->dc; c.rows = rows;
+      c.fem = set.ob->p; c.c = h->dc.p; c.rows = rows;
       c.n = cnt; c.L = L; c.LW = LW; c.A = A; c.K = K;
       c.dfe = d_df; c.pll = d_pll;
       hipLaunchKernelGGL(mutagenesis_combine_kernel, dim3(std::max(1, std::min((cnt + 3) / 4, h->num_cu * 8))), dim3(256), 0, set.st, c);
@@ -3397,13 +3306,13 @@ int crbm_ais(crbm_handle* h, int32_t L, int32_t runs, uint32_t run_offset, const
   HIPCHK(h->ais_state.ensure(nstate));
   HIPCHK(hipMemcpyAsync(h->ais_betas.p, betas, (size_t)nbetas * sizeof(float), hipMemcpyHostToDevice, h->stream));
   if (base_c) HIPCHK(hipMemcpyAsync(h->ais_base.p, base_c, 4 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  else HIPCHK(hipMemcpyAsync(h->ais_base.p, h->dc, 4 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  else HIPCHK(hipMemcpyAsync(h->ais_base.p, h->dc.p, 4 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   if (t0 > 0) {
     HIPCHK(hipMemcpyAsync(h->ais_state.p, state, nstate, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->ais_logw.p, logw, (size_t)runs * sizeof(float), hipMemcpyHostToDevice, h->stream));
   }
   AisArgs a;
-  a.tables = h->d_tables; a.base_c = h->ais_base.p; a.betas = h->ais_betas.p;
+  a.tables = h->d_tables.p; a.base_c = h->ais_base.p; a.betas = h->ais_betas.p;
   a.state = h->ais_state.p; a.logw = h->ais_logw.p;
   a.runs = runs; a.L = L; a.Lh = L - h->M + 1;
   a.nvb = al.nvb; a.Lrow = al.Lrow; a.LWs = al.LWs; a.run_words = al.run_words;
@@ -3426,7 +3335,7 @@ int crbm_eval_params(crbm_handle* h, float* twn, float* ic, float* medic) {
   ARGCHK(twn && ic && medic, "null argument");
   const int K = h->K, M = h->M;
   std::vector<float> W((size_t)h->KAM);
-  HIPCHK(hipMemcpyAsync(W.data(), h->dW, W.size() * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(W.data(), h->dW.p, W.size() * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   // convRBM.py:475-485 on A*K*M numbers: host arithmetic in double
   const int A = h->A;
@@ -3505,8 +3414,8 @@ int crbm_comm_broadcast_state(crbm_handle* h, int32_t root) {
   ENTER();
   if (!h->comm) return CRBM_OK;
   ARGCHK(root >= 0 && root < h->nranks, "root out of range");
-  struct { float* p; size_t n; } bufs[] = {{h->dW, (size_t)h->KAM}, {h->db, (size_t)h->K}, {h->dc, (size_t)h->A},
-                                           {h->dvW, (size_t)h->KAM}, {h->dvb, (size_t)h->K}, {h->dvc, (size_t)h->A}};
+  struct { float* p; size_t n; } bufs[] = {{h->dW.p, (size_t)h->KAM}, {h->db.p, (size_t)h->K}, {h->dc.p, (size_t)h->A},
+                                           {h->dvW.p, (size_t)h->KAM}, {h->dvb.p, (size_t)h->K}, {h->dvc.p, (size_t)h->A}};
   for (auto& b : bufs) {
     ncclResult_t r = g_rccl.Broadcast(b.p, b.p, b.n, ncclFloat, root, h->comm, h->stream);
     if (r != ncclSuccess) return fail(h, CRBM_ERR_RCCL, std::string("ncclBroadcast: ") + g_rccl.GetErrorString(r));
@@ -3527,9 +3436,9 @@ int crbm_ipc_export(crbm_handle* h, uint8_t handle[CRBM_IPC_HANDLE_BYTES]) {
   // flags and status start from zero with every attachment (the step count does too): cleared here, before the
   // handle leaves -- no peer pushes into this buffer before it has seen the handles of all ranks
   HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipMemset(h->ipc_buf, 0, ipc_bytes(h)));
+  HIPCHK(hipMemset(h->ipc_buf.p, 0, ipc_bytes(h)));
   hipIpcMemHandle_t mh;
-  HIPCHK(hipIpcGetMemHandle(&mh, h->ipc_buf));
+  HIPCHK(hipIpcGetMemHandle(&mh, h->ipc_buf.p));
   memcpy(handle, &mh, sizeof(mh));
   return CRBM_OK;
 }
@@ -3542,13 +3451,11 @@ int crbm_ipc_attach(crbm_handle* h, const uint8_t* handles, int32_t nranks, int3
   int rc = ipc_allocate(h);
   if (rc) return rc;
   for (int r = 0; r < nranks; ++r) {
-    if (r == rank) { h->ipc_peer[r] = h->ipc_buf; continue; }
+    if (r == rank) { h->ipc_peer.set_own(r, h->ipc_buf.p); continue; }
     hipIpcMemHandle_t mh;
     memcpy(&mh, handles + (size_t)r * CRBM_IPC_HANDLE_BYTES, sizeof(mh));
-    void* p = nullptr;
-    hipError_t e = hipIpcOpenMemHandle(&p, mh, hipIpcMemLazyEnablePeerAccess);
+    hipError_t e = h->ipc_peer.open(r, mh);
     if (e != hipSuccess) return fail(h, CRBM_ERR_HIP, std::string("hipIpcOpenMemHandle (rank ") + std::to_string(r) + "): " + hipGetErrorString(e));
-    h->ipc_peer[r] = p;
   }
   h->nranks = nranks; h->rank = rank;
   h->ipc_on = true;
@@ -3567,10 +3474,7 @@ int crbm_ipc_attach(crbm_handle* h, const uint8_t* handles, int32_t nranks, int3
 int crbm_ipc_detach(crbm_handle* h) {
   ENTER();
   HIPCHK(hipStreamSynchronize(h->stream));
-  for (int r = 0; r < IPC_MAX_RANKS; ++r) {
-    if (h->ipc_peer[r] && h->ipc_peer[r] != h->ipc_buf) (void)hipIpcCloseMemHandle(h->ipc_peer[r]);
-    h->ipc_peer[r] = nullptr;
-  }
+  h->ipc_peer.close();
   h->ipc_on = false;
   h->nranks = 1; h->rank = 0;
   return CRBM_OK;
@@ -3580,10 +3484,10 @@ int crbm_ipc_status(crbm_handle* h, int32_t* timed_out) {
   ENTER();
   ARGCHK(timed_out, "null argument");
   *timed_out = 0;
-  if (!h->ipc_buf) return CRBM_OK;
+  if (!h->ipc_buf.p) return CRBM_OK;
   uint32_t st = 0;
   HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipMemcpy(&st, ipc_status_of(h->ipc_buf, h), sizeof(st), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&st, ipc_status_of(h->ipc_buf.p, h), sizeof(st), hipMemcpyDeviceToHost));
   *timed_out = (int32_t)st;
   return CRBM_OK;
 }
@@ -3602,7 +3506,7 @@ int crbm_train_local(crbm_handle* h, const float* D, int32_t n, int32_t L, float
   }
   rc = train_local_dev(h, h->letters.p, n, L);
   if (rc) return rc;
-  rc = copy_out(h, sums_out, h->d_sums, (size_t)h->sl.count);
+  rc = copy_out(h, sums_out, h->d_sums.p, (size_t)h->sl.count);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   return CRBM_OK;
@@ -3611,7 +3515,7 @@ int crbm_train_local(crbm_handle* h, const float* D, int32_t n, int32_t L, float
 int crbm_train_apply(crbm_handle* h, const float* sums_in, int32_t L_data) {
   ENTER();
   ARGCHK(sums_in && L_data >= h->M, "bad argument");
-  HIPCHK(hipMemcpyAsync(h->d_sums, sums_in, (size_t)h->sl.count * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_sums.p, sums_in, (size_t)h->sl.count * 4, hipMemcpyHostToDevice, h->stream));
   int rc = launch_update(h, L_data);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -3625,7 +3529,7 @@ int crbm_time_allreduce(crbm_handle* h, int32_t launches, float* total_ms) {
   if (!h->comm) return CRBM_OK;
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   for (int i = 0; i < launches; ++i) {
-    ncclResult_t r = g_rccl.AllReduce(h->d_sums, h->d_sums, (size_t)h->sl.count, ncclFloat, ncclSum, h->comm, h->stream);
+    ncclResult_t r = g_rccl.AllReduce(h->d_sums.p, h->d_sums.p, (size_t)h->sl.count, ncclFloat, ncclSum, h->comm, h->stream);
     if (r != ncclSuccess) return fail(h, CRBM_ERR_RCCL, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
   }
   HIPCHK(hipEventRecord(h->ev1, h->stream));
@@ -3671,23 +3575,27 @@ int crbm_copy_bandwidth(crbm_handle* h, int64_t bytes, int32_t reps, float* gb_p
   ENTER();
   ARGCHK(bytes >= (1 << 20) && reps >= 1 && gb_per_s, "bad argument");
   const size_t n4 = (size_t)bytes / 16;
-  float4 *src = nullptr, *dst = nullptr;
-  HIPCHK(hipMalloc((void**)&src, n4 * 16));
-  hipError_t e = hipMalloc((void**)&dst, n4 * 16);
-  if (e != hipSuccess) { (void)hipFree(src); return fail(h, CRBM_ERR_HIP, "hipMalloc (copy buffer)"); }
-  (void)hipMemsetAsync(src, 1, n4 * 16, h->stream);
+  DevBuf<float4> src, dst;
+  HIPCHK(src.alloc(n4));
+  HIPCHK(dst.alloc(n4));
+  (void)hipMemsetAsync(src.p, 1, n4 * 16, h->stream);
   const unsigned grid = (unsigned)((n4 + 1023) / 1024);
   for (int i = 0; i < 1 + reps; ++i) {
     if (i == 1) (void)hipEventRecord(h->ev0, h->stream);
-    hipLaunchKernelGGL(copy_float4_kernel, dim3(grid), dim3(256), 0, h->stream, src, dst, n4);
+    hipLaunchKernelGGL(copy_float4_kernel, dim3(grid), dim3(256), 0, h->stream, src.p, dst.p, n4);
   }
   (void)hipEventRecord(h->ev1, h->stream);
-  e = hipEventSynchronize(h->ev1);
+  hipError_t e = hipEventSynchronize(h->ev1);
   float ms = 0.f;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, h->ev0, h->ev1);
-  (void)hipFree(src); (void)hipFree(dst);
   if (e != hipSuccess) return fail(h, CRBM_ERR_HIP, std::string("copy bandwidth: ") + hipGetErrorString(e));
   *gb_per_s = (float)(2.0 * (double)n4 * 16.0 * reps / (ms * 1e-3) / 1e9);   // bytes read + written
+  return CRBM_OK;
+}
+
+int crbm_live_resources(int64_t counts[5]) {      // buffers, bytes, streams, events, modules (crbm_own.h: LiveKind)
+  if (!counts) return CRBM_ERR_INVALID;
+  for (int i = 0; i < LIVE_KINDS; ++i) counts[i] = live(i).load(std::memory_order_relaxed);
   return CRBM_OK;
 }
 
@@ -3705,7 +3613,7 @@ int crbm_last_shader_clock(crbm_handle* h, float* mhz) {
   ARGCHK(mhz, "null argument");
   *mhz = 0.f;
   HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipMemcpy(h->probe_last, h->d_probe, sizeof(h->probe_last), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(h->probe_last, h->d_probe.p, sizeof(h->probe_last), hipMemcpyDeviceToHost));
   const unsigned long long ticks = h->probe_last[0] - h->probe_base[0], cycles = h->probe_last[1] - h->probe_base[1];
   if (ticks) *mhz = (float)((double)cycles / ((double)ticks / (h->wall_khz / 1000.0)));
   return CRBM_OK;
@@ -3724,15 +3632,13 @@ int64_t crbm_gibbs_state_bytes(const crbm_handle* h) {
 namespace {
 
 // device buffers of one call, freed whichever way the call ends
-struct TsneScratch {
-  std::vector<void*> ptrs;
-  ~TsneScratch() { for (void* p : ptrs) (void)hipFree(p); }
+struct CallBufs {
+  std::deque<DevBuf<unsigned char>> bufs;
   template <typename T>
   hipError_t get(T** out, size_t count) {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) ptrs.push_back(p);
-    *out = static_cast<T*>(p);
+    bufs.emplace_back();
+    const hipError_t e = bufs.back().alloc(std::max<size_t>(count, 1) * sizeof(T));
+    *out = reinterpret_cast<T*>(bufs.back().p);
     return e;
   }
 };
@@ -3752,7 +3658,7 @@ int crbm_tsne_neighbors(crbm_handle* h, const float* X, int64_t n, int32_t D, in
   while (waves > 1 && tsne::knn_lds_bytes(D, k, waves) > 128 * 1024) waves >>= 1;
   const size_t lds = tsne::knn_lds_bytes(D, k, waves);
   ARGCHK(lds <= 160 * 1024, "k and D leave no room in the LDS");
-  TsneScratch s;
+  CallBufs s;
   float *dX = nullptr, *dd2 = nullptr;
   int32_t* didx = nullptr;
   HIPCHK(s.get(&dX, (size_t)n * D));
@@ -3774,7 +3680,7 @@ int crbm_tsne_affinities(crbm_handle* h, const float* d2, int64_t n, int32_t k, 
   ARGCHK(d2 && p && beta, "null argument");
   if (const char* why = tsne::affinities_refusal(n, k, perplexity)) return fail(h, CRBM_ERR_INVALID, why);
   for (int64_t e = 0; e < n * k; ++e) ARGCHK(std::isfinite(d2[e]) && d2[e] >= 0.f, "a distance is negative or not finite");
-  TsneScratch s;
+  CallBufs s;
   float *dd2 = nullptr, *dp = nullptr, *dbeta = nullptr;
   HIPCHK(s.get(&dd2, (size_t)n * k));
   HIPCHK(s.get(&dp, (size_t)n * k));
@@ -3801,7 +3707,7 @@ int crbm_tsne_descend(crbm_handle* h, int64_t n, const int64_t* indptr, const in
   const size_t nnz = (size_t)indptr[n];
   const int S = tsne::slices(n);
   const int64_t chunks = tsne::sum_chunks(n);
-  TsneScratch s;
+  CallBufs s;
   int64_t* dptr = nullptr;
   int32_t* dind = nullptr;
   float* dval = nullptr;
@@ -3885,27 +3791,14 @@ int crbm_tsne_descend_ms(crbm_handle* h, float* ms) {
 namespace {
 
 // events of one call, destroyed whichever way the call ends
-struct BgEvents {
-  hipEvent_t walk[2] = {nullptr, nullptr};             // a set's walk kernel has left the carry of the next segment
-  hipEvent_t t[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // around a set's kernels
-  ~BgEvents() {
-    for (hipEvent_t e : walk)
-      if (e) (void)hipEventDestroy(e);
-    for (auto& set : t)
-      for (hipEvent_t e : set)
-        if (e) (void)hipEventDestroy(e);
-  }
+struct CallEvents {
+  Event walk[2];                       // a set's walk kernel has left the carry of the next segment
+  Event t[2][2];                       // around a set's kernels
   hipError_t create() {
-    for (auto& e : walk) {
-      const hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-      if (rc != hipSuccess) return rc;
-    }
-    for (auto& set : t)
-      for (auto& e : set) {
-        const hipError_t rc = hipEventCreate(&e);
-        if (rc != hipSuccess) return rc;
-      }
-    return hipSuccess;
+    hipError_t rc = hipSuccess;
+    for (Event& e : walk) if (rc == hipSuccess) rc = e.create_untimed();
+    for (auto& set : t) for (Event& e : set) if (rc == hipSuccess) rc = e.create();
+    return rc;
   }
 };
 
@@ -3945,12 +3838,12 @@ int crbm_stream_kmer_counts(crbm_handle* h, const uint8_t* codes, int64_t T, int
   ENTER();
   if (const char* why = bg::counts_refusal(codes, T, order, counts)) return fail(h, CRBM_ERR_INVALID, std::string("crbm_stream_kmer_counts: ") + why);
   const int slots = bg::kmer_slots(order), seg = bg_segment(T, 1), nsets = seg < T ? 2 : 1;
-  TsneScratch s;
+  CallBufs s;
   unsigned long long* dcounts = nullptr;
   uint8_t* dcodes[2] = {nullptr, nullptr};
   HIPCHK(s.get(&dcounts, (size_t)slots));
   for (int i = 0; i < nsets; ++i) HIPCHK(s.get(&dcodes[i], (size_t)seg + order));
-  BgEvents ev;
+  CallEvents ev;
   HIPCHK(ev.create());
   HIPCHK(hipMemsetAsync(dcounts, 0, (size_t)slots * 8, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));               // (the second stream adds to the counters too)
@@ -3995,7 +3888,7 @@ int crbm_background_sample(crbm_handle* h, const uint32_t* thr, int32_t order, i
   const int64_t seg_chunks = ((int64_t)seg + chunk - 1) / chunk, seg_groups = (seg_chunks + bg::GROUP - 1) / bg::GROUP;
   uint32_t rows[4 * bg::contexts(bg::MAX_ORDER)];
   bg::build_rows(thr, order, rows);
-  TsneScratch s;
+  CallBufs s;
   uint4* drows = nullptr;
   uint8_t *dcarry = nullptr, *dtmpl[2] = {nullptr, nullptr}, *dout[2] = {nullptr, nullptr}, *dcmap[2] = {nullptr, nullptr},
           *dgmap[2] = {nullptr, nullptr}, *dcentry[2] = {nullptr, nullptr}, *dgentry[2] = {nullptr, nullptr};
@@ -4009,7 +3902,7 @@ int crbm_background_sample(crbm_handle* h, const uint32_t* thr, int32_t order, i
     HIPCHK(s.get(&dcentry[i], (size_t)seg_chunks));
     HIPCHK(s.get(&dgentry[i], (size_t)seg_groups));
   }
-  BgEvents ev;
+  CallEvents ev;
   HIPCHK(ev.create());
   HIPCHK(hipMemcpyAsync(drows, rows, (size_t)NS * 16, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemsetAsync(dcarry, 0, 4, h->stream));       // the empty context
@@ -4075,7 +3968,7 @@ int crbm_score_distribution(crbm_handle* h, const int32_t* q, int32_t R, int32_t
   const int NS = plan.contexts, variant = env_int("CRBM_NULL_VARIANT", null::VARIANT_DEFAULT), rpg = plan.rows_per_group;
   std::vector<null::Pred> table((size_t)NS * null::PREDS);
   null::build_table(order, trans, table.data());
-  TsneScratch s;
+  CallBufs s;
   int32_t *dq = nullptr, *dreach = nullptr;
   null::Pred* dtable = nullptr;
   double *dinit = nullptr, *state[2] = {nullptr, nullptr}, *dpmf = nullptr;
@@ -4086,7 +3979,7 @@ int crbm_score_distribution(crbm_handle* h, const int32_t* q, int32_t R, int32_t
   HIPCHK(s.get(&state[0], (size_t)plan.state_elems));
   HIPCHK(s.get(&state[1], (size_t)plan.state_elems));
   HIPCHK(s.get(&dpmf, (size_t)rpg * (size_t)G));
-  BgEvents ev;
+  CallEvents ev;
   HIPCHK(ev.create());
   const hipStream_t st = h->stream;
   HIPCHK(hipMemcpyAsync(dq, q, (size_t)R * M * 16, hipMemcpyHostToDevice, st));

@@ -24,10 +24,12 @@
 #include <unordered_map>
 #include <vector>
 
+#include "crbm_own.h"
+
 namespace crbm {
 
 struct JitKernels {
-  hipModule_t module = nullptr;
+  Module module;
   hipFunction_t build_tables = nullptr, update_tables = nullptr, update_tables_ipc = nullptr, hgv = nullptr, gibbs = nullptr /* dense top-down; null if the model has none */,
                 build_gather_solo = nullptr /* gather table of the solo letter grouping */, slab_hgv = nullptr, slab_tables = nullptr, slab_stats_data = nullptr, slab_stats_model = nullptr, slab_fe = nullptr /* the model as a slab of a larger one: empty beyond 64 motifs */,
                 gibbs_sparse = nullptr, gibbs_sparse_stats = nullptr /* empty unless Cfg::FUSE_STATS */, train_local = nullptr /* ditto */, stats_mfma_data = nullptr, stats_mfma_model = nullptr,
@@ -248,59 +250,59 @@ inline int jit_compile_source(const std::string& stub, std::vector<char>* code, 
   return 0;
 }
 
-inline int jit_load(int K, int M, int DS, int G, int GS, int POOL, int gibbs_wpe, int gibbs_tb, JitKernels* out, std::string* err, bool slab = false) {
-  std::vector<char> code;
-  if (jit_compile(K, M, DS, G, GS, POOL, gibbs_wpe, gibbs_tb, &code, &out->from_cache, &out->cache_file, err, slab) != 0) return -1;
-  hipError_t e = hipModuleLoadData(&out->module, code.data());
+// load a code object and look its kernels up (a symbol without a target is skipped)
+struct JitSym { const char* name; hipFunction_t* f; };
+inline int jit_bind(Module* m, const std::vector<char>& code, const JitSym* syms, size_t n, std::string* err) {
+  hipError_t e = m->load(code.data());
   if (e != hipSuccess) {
     *err = std::string("hipModuleLoadData: ") + hipGetErrorString(e);
     return -1;
   }
-  struct { const char* name; hipFunction_t* f; } syms[] = {
-      {"crbm_build_tables", &out->build_tables}, {"crbm_build_gather_solo", &out->build_gather_solo}, {"crbm_update_tables", &out->update_tables}, {"crbm_update_tables_ipc", &out->update_tables_ipc}, {"crbm_hgv", &out->hgv}, {"crbm_slab_hgv", &out->slab_hgv}, {"crbm_slab_tables", &out->slab_tables}, {"crbm_slab_stats_data", &out->slab_stats_data}, {"crbm_slab_stats_model", &out->slab_stats_model}, {"crbm_slab_fe", &out->slab_fe}, {"crbm_gibbs", &out->gibbs},
-      {"crbm_gibbs_sparse", &out->gibbs_sparse}, {"crbm_gibbs_sparse_stats", &out->gibbs_sparse_stats}, {"crbm_train_local", &out->train_local},
-      {"crbm_stats_mfma_data", &out->stats_mfma_data},
-      {"crbm_stats_mfma_model", &out->stats_mfma_model}, {"crbm_free_energy", &out->free_energy},
-      {"crbm_hit_summary", &out->hit_summary}, {"crbm_motif_sites", &out->motif_sites},
-      {"crbm_mutagenesis", &out->mutagenesis}, {"crbm_ais", &out->ais}, {"crbm_scan_sites", &out->scan_sites},
-      {"crbm_scan_hist", &out->scan_hist}, {"crbm_scan_records", &out->scan_records}, {"crbm_variant_effects", &out->variant_effects},
-      {"crbm_allele_effects", &out->allele_effects}};
-  for (auto& s : syms) {
-    e = hipModuleGetFunction(s.f, out->module, s.name);
+  for (size_t i = 0; i < n; ++i) {
+    if (!syms[i].f) continue;
+    e = hipModuleGetFunction(syms[i].f, *m, syms[i].name);
     if (e != hipSuccess) {
-      *err = std::string("hipModuleGetFunction(") + s.name + "): " + hipGetErrorString(e);
+      *err = std::string("hipModuleGetFunction(") + syms[i].name + "): " + hipGetErrorString(e);
       return -1;
     }
   }
   return 0;
 }
 
+inline int jit_load(int K, int M, int DS, int G, int GS, int POOL, int gibbs_wpe, int gibbs_tb, JitKernels* out, std::string* err, bool slab = false) {
+  std::vector<char> code;
+  JitKernels k;      // handed to *out once every function is found: a failure on the way leaves nothing loaded
+  if (jit_compile(K, M, DS, G, GS, POOL, gibbs_wpe, gibbs_tb, &code, &k.from_cache, &k.cache_file, err, slab) != 0) return -1;
+  const JitSym syms[] = {
+      {"crbm_build_tables", &k.build_tables}, {"crbm_build_gather_solo", &k.build_gather_solo}, {"crbm_update_tables", &k.update_tables}, {"crbm_update_tables_ipc", &k.update_tables_ipc}, {"crbm_hgv", &k.hgv}, {"crbm_slab_hgv", &k.slab_hgv}, {"crbm_slab_tables", &k.slab_tables}, {"crbm_slab_stats_data", &k.slab_stats_data}, {"crbm_slab_stats_model", &k.slab_stats_model}, {"crbm_slab_fe", &k.slab_fe}, {"crbm_gibbs", &k.gibbs},
+      {"crbm_gibbs_sparse", &k.gibbs_sparse}, {"crbm_gibbs_sparse_stats", &k.gibbs_sparse_stats}, {"crbm_train_local", &k.train_local},
+      {"crbm_stats_mfma_data", &k.stats_mfma_data},
+      {"crbm_stats_mfma_model", &k.stats_mfma_model}, {"crbm_free_energy", &k.free_energy},
+      {"crbm_hit_summary", &k.hit_summary}, {"crbm_motif_sites", &k.motif_sites},
+      {"crbm_mutagenesis", &k.mutagenesis}, {"crbm_ais", &k.ais}, {"crbm_scan_sites", &k.scan_sites},
+      {"crbm_scan_hist", &k.scan_hist}, {"crbm_scan_records", &k.scan_records}, {"crbm_variant_effects", &k.variant_effects},
+      {"crbm_allele_effects", &k.allele_effects}};
+  if (jit_bind(&k.module, code, syms, sizeof(syms) / sizeof(syms[0]), err) != 0) return -1;
+  *out = std::move(k);
+  return 0;
+}
+
 // the geometry-specialised chain kernels of a handle; a function stays null where the plan has no such launch shape
 struct JitGeoKernels {
-  hipModule_t module = nullptr;
+  Module module;
   hipFunction_t gibbs_sparse = nullptr, gibbs_sparse_stats = nullptr, train_local = nullptr;
 };
 inline int jit_load_geo(int K, int M, int DS, int POOL, int gibbs_wpe, const JitGeo& plain, const JitGeo& fused, JitGeoKernels* out, std::string* err) {
   if (!plain.on() && !fused.on()) return 0;
   std::vector<char> code;
   bool cached = false;
+  JitGeoKernels k;
   if (jit_compile_geo(K, M, DS, POOL, gibbs_wpe, plain, fused, &code, &cached, nullptr, err) != 0) return -1;
-  hipError_t e = hipModuleLoadData(&out->module, code.data());
-  if (e != hipSuccess) {
-    *err = std::string("hipModuleLoadData: ") + hipGetErrorString(e);
-    return -1;
-  }
-  struct { bool want; const char* name; hipFunction_t* f; } syms[] = {
-      {plain.on(), "crbm_gibbs_sparse_geo", &out->gibbs_sparse}, {fused.on(), "crbm_gibbs_sparse_stats_geo", &out->gibbs_sparse_stats},
-      {fused.on(), "crbm_train_local_geo", &out->train_local}};
-  for (auto& s : syms) {
-    if (!s.want) continue;
-    e = hipModuleGetFunction(s.f, out->module, s.name);
-    if (e != hipSuccess) {
-      *err = std::string("hipModuleGetFunction(") + s.name + "): " + hipGetErrorString(e);
-      return -1;
-    }
-  }
+  const JitSym syms[] = {     // (no target: the plan has no such launch shape)
+      {"crbm_gibbs_sparse_geo", plain.on() ? &k.gibbs_sparse : nullptr}, {"crbm_gibbs_sparse_stats_geo", fused.on() ? &k.gibbs_sparse_stats : nullptr},
+      {"crbm_train_local_geo", fused.on() ? &k.train_local : nullptr}};
+  if (jit_bind(&k.module, code, syms, sizeof(syms) / sizeof(syms[0]), err) != 0) return -1;
+  *out = std::move(k);
   return 0;
 }
 

@@ -472,6 +472,10 @@ int crbm_last_shader_clock(crbm_handle* h, float* mhz);
 /* Chain kernel launches of this handle so far by the form of their geometry: compiled in (the kernels specialised on the
  * handle's launch shapes; CRBM_GEOM) and read from the arguments (every other launch).  Either may be null. */
 int crbm_geometry_launches(const crbm_handle* h, int64_t* compiled_in, int64_t* run_time);
+/* GPU resources this process holds through the library right now, over all handles and calls in flight:
+ * counts[0..4] = device buffers, their bytes, streams, events, loaded code objects.  Every number returns to what it was
+ * once the handles created since have been destroyed (a leak shows as a difference).  Needs no handle and no GPU. */
+int crbm_live_resources(int64_t counts[5]);
 /* Actual bytes of chain state one Gibbs launch reads+writes in HBM. */
 int64_t crbm_gibbs_state_bytes(const crbm_handle* h);
 
