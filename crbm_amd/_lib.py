@@ -57,6 +57,7 @@ _U8P = ctypes.POINTER(ctypes.c_uint8)
 _I64 = ctypes.c_int64
 _I32P = ctypes.POINTER(ctypes.c_int32)
 _I64P = ctypes.POINTER(ctypes.c_int64)
+_U16P = ctypes.POINTER(ctypes.c_uint16)
 
 
 class CrbmSite(ctypes.Structure):
@@ -156,6 +157,11 @@ SIGNATURES = {
     "crbm_score_distribution": (_I32, [_H, _I32P, _I32, _I32, _I32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _I64,
                                        ctypes.POINTER(ctypes.c_double)]),
     "crbm_null_ms": (_I32, [_H, _F]),
+    "crbm_motif_compare": (_I32, [_H, _U16P, _I32P, _I32, _U16P, _I32P, _I32, _I32, _I32, _I32, ctypes.c_double,
+                                  ctypes.POINTER(ctypes.c_double), _I32P, ctypes.POINTER(ctypes.c_int8), _I32P, _I32P]),
+    "crbm_motif_compare_null": (_I32, [_H, _U16P, _I32, _U16P, _I32P, _I32, _I32, _I32, ctypes.c_double, ctypes.POINTER(_U32),
+                                       ctypes.POINTER(ctypes.c_double)]),
+    "crbm_compare_ms": (_I32, [_H, _F, _F]),
 }
 
 _lib = None

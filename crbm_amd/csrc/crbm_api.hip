@@ -10,6 +10,7 @@
 #include "crbm_tsne.h"
 #include "crbm_background.h"
 #include "crbm_null.h"
+#include "crbm_compare.h"
 #include "../../include/crbm_amd.h"
 
 #include <dlfcn.h>
@@ -237,6 +238,7 @@ struct crbm_handle {
   uint64_t slab_tables_version = 0;
   float tsne_ms = 0.f;                 // device time of the iterations of the last crbm_tsne_descend call (HIP events)
   float null_ms = 0.f;                 // device time of the kernels of the last crbm_score_distribution call
+  float compare_ms[4] = {0.f, 0.f, 0.f, 0.f};   // ... of the last crbm_motif_compare / _null call: all kernels; counts, null, placements
   float bg_ms = 0.f;                   // device time of the kernels of the last crbm_stream_kmer_counts / crbm_background_sample call
   std::string slab_note;               // why the slabs are off, if they are (crbm_launch_info prints nothing of it; a debugging aid)
   std::string err;
@@ -4027,6 +4029,147 @@ int crbm_score_distribution(crbm_handle* h, const int32_t* q, int32_t R, int32_t
 int crbm_null_ms(crbm_handle* h, float* ms) {
   if (!h || !ms) return CRBM_ERR_INVALID;
   *ms = h->null_ms;
+  return CRBM_OK;
+}
+
+}  // extern "C"
+
+// ---- motif comparison (crbm_compare.h): the handle lends its device, its main stream and its error string -------------
+namespace {
+
+// The three stages for every group of queries.  null_of >= 0: crbm_motif_compare_null -- stages one and two only, the
+// counters and tables of the single query copied out.
+int compare_run(crbm_handle* h, const compare::Plan& plan, const uint16_t* qcols, const int32_t* qstart, int32_t K, const uint16_t* tcols,
+                const int32_t* tstart, int32_t N, int32_t bins, int32_t both, int32_t min_overlap, double invC, double* p_min,
+                int32_t* offset, int8_t* strand, int32_t* overlap, int32_t* n_off, uint32_t* counts_out, double* tail_out) {
+  for (float& ms : h->compare_ms) ms = 0.f;
+  const bool place = counts_out == nullptr;
+  CallBufs s;
+  uint2 *dq = nullptr, *dt = nullptr;
+  int32_t *dqs = nullptr, *dts = nullptr, *doff = nullptr, *dovl = nullptr, *dnoff = nullptr;
+  int64_t* dbase = nullptr;
+  uint32_t* dcounts = nullptr;
+  double *dtables = nullptr, *dp = nullptr;
+  int8_t* dstrand = nullptr;
+  const size_t rows_out = place ? (size_t)plan.rows_max * (size_t)N : 1;
+  HIPCHK(s.get(&dq, (size_t)qstart[K]));
+  HIPCHK(s.get(&dt, (size_t)plan.tcols));
+  HIPCHK(s.get(&dqs, (size_t)K + 1));
+  HIPCHK(s.get(&dts, (size_t)N + 1));
+  HIPCHK(s.get(&dbase, (size_t)K));
+  HIPCHK(s.get(&dcounts, (size_t)plan.count_elems_max));
+  HIPCHK(s.get(&dtables, (size_t)plan.table_elems_max));
+  HIPCHK(s.get(&dp, rows_out));
+  HIPCHK(s.get(&doff, rows_out));
+  HIPCHK(s.get(&dstrand, rows_out));
+  HIPCHK(s.get(&dovl, rows_out));
+  HIPCHK(s.get(&dnoff, rows_out));
+  CallEvents ev;
+  HIPCHK(ev.create());
+  const hipEvent_t mark[4] = {ev.t[0][0], ev.t[0][1], ev.t[1][0], ev.t[1][1]};
+  const hipStream_t st = h->stream;
+  HIPCHK(hipMemcpyAsync(dq, qcols, (size_t)qstart[K] * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dt, tcols, (size_t)plan.tcols * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dqs, qstart, ((size_t)K + 1) * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dts, tstart, ((size_t)N + 1) * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dbase, plan.table_base.data(), (size_t)K * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(compare::counts_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)compare::counts_lds(compare::MAX_WIDTH, compare::MAX_BINS)));
+  const compare::Motifs motifs{dq, dqs, dt, dts};
+  double total[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int g = 0; g < plan.groups(); ++g) {
+    const int q0 = plan.group_start[(size_t)g], rows = plan.group_start[(size_t)g + 1] - q0;
+    const int wq = compare::widest(qstart, q0, q0 + rows);
+    const size_t ncounts = (size_t)(qstart[q0 + rows] - qstart[q0]) * (size_t)bins;
+    HIPCHK(hipEventRecord(mark[0], st));
+    HIPCHK(hipMemsetAsync(dcounts, 0, ncounts * 4, st));
+    compare::CountArgs c;
+    c.m = motifs; c.counts = dcounts; c.tcols = plan.tcols; c.q0 = q0; c.bins = bins; c.both = both;
+    hipLaunchKernelGGL(compare::counts_kernel, dim3(compare::count_blocks(plan.tcols), (unsigned)rows), dim3(256),
+                       compare::counts_lds(wq, bins), st, c);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(mark[1], st));
+    compare::NullArgs n;
+    n.qstart = dqs; n.counts = dcounts; n.tables = dtables; n.table_base = dbase; n.invC = invC; n.q0 = q0; n.bins = bins; n.l = 0; n.tiles = 0;
+    for (int l = 1; l <= wq; ++l) {
+      n.l = l;
+      n.tiles = (int32_t)compare::conv_tiles(bins, l);
+      hipLaunchKernelGGL(compare::conv_kernel, dim3((unsigned)(n.tiles * (wq - l + 1)), (unsigned)rows), dim3(256),
+                         compare::conv_lds(bins), st, n);
+    }
+    hipLaunchKernelGGL(compare::tail_kernel, dim3((unsigned)((wq * (wq + 1) / 2 + 63) / 64), (unsigned)rows), dim3(64), 0, st, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(mark[2], st));
+    if (place) {
+      compare::PlaceArgs a;
+      a.m = motifs; a.tables = dtables; a.table_base = dbase;
+      a.p_min = dp; a.offset = doff; a.strand = dstrand; a.overlap = dovl; a.n_off = dnoff;
+      a.q0 = q0; a.N = N; a.bins = bins; a.both = both; a.min_overlap = min_overlap; a.tile = plan.tile;
+      a.diagonals = wq + plan.width_max_targets - 1;
+      hipLaunchKernelGGL(compare::place_kernel, dim3((unsigned)((N + plan.tile - 1) / plan.tile), (unsigned)rows), dim3(256),
+                         compare::place_lds(plan.tile, a.diagonals), st, a);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(mark[3], st));
+    if (place) {
+      const size_t at = (size_t)q0 * (size_t)N, cnt = (size_t)rows * (size_t)N;
+      HIPCHK(hipMemcpyAsync(p_min + at, dp, cnt * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(offset + at, doff, cnt * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(strand + at, dstrand, cnt, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(overlap + at, dovl, cnt * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(n_off + at, dnoff, cnt * 4, hipMemcpyDeviceToHost, st));
+    } else {
+      HIPCHK(hipMemcpyAsync(counts_out, dcounts, ncounts * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(tail_out, dtables, (size_t)compare::table_elems(bins, qstart[1]) * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < 3; ++i) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, mark[i], mark[i + 1]));
+      total[i + 1] += ms;
+      total[0] += ms;
+    }
+  }
+  for (int i = 0; i < 4; ++i) h->compare_ms[i] = (float)total[i];
+  return CRBM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crbm_motif_compare(crbm_handle* h, const uint16_t* qcols, const int32_t* qstart, int32_t K, const uint16_t* tcols,
+                       const int32_t* tstart, int32_t N, int32_t bins, int32_t both, int32_t min_overlap, double invC,
+                       double* p_min, int32_t* offset, int8_t* strand, int32_t* overlap, int32_t* n_off) {
+  ENTER();
+  compare::Plan plan;
+  if (const char* why = compare::plan_or_refusal(qcols, qstart, K, tcols, tstart, N, bins, both, min_overlap, invC,
+                                                 p_min && offset && strand && overlap && n_off,
+                                                 compare::env_i64("CRBM_COMPARE_BYTES", compare::BYTES_DEFAULT),
+                                                 compare::env_i64("CRBM_COMPARE_TILE", compare::TILE_DEFAULT), &plan))
+    return fail(h, CRBM_ERR_INVALID, std::string("crbm_motif_compare: ") + why);
+  return compare_run(h, plan, qcols, qstart, K, tcols, tstart, N, bins, both, min_overlap, invC, p_min, offset, strand, overlap, n_off,
+                     nullptr, nullptr);
+}
+
+int crbm_motif_compare_null(crbm_handle* h, const uint16_t* qcols, int32_t m, const uint16_t* tcols, const int32_t* tstart, int32_t N,
+                            int32_t bins, int32_t both, double invC, uint32_t* counts, double* tail) {
+  ENTER();
+  const int32_t qstart[2] = {0, m};
+  compare::Plan plan;
+  if (const char* why = compare::plan_or_refusal(qcols, qstart, 1, tcols, tstart, N, bins, both, 1, invC, counts && tail,
+                                                 compare::env_i64("CRBM_COMPARE_BYTES", compare::BYTES_DEFAULT),
+                                                 compare::env_i64("CRBM_COMPARE_TILE", compare::TILE_DEFAULT), &plan))
+    return fail(h, CRBM_ERR_INVALID, std::string("crbm_motif_compare_null: ") + why);
+  return compare_run(h, plan, qcols, qstart, 1, tcols, tstart, N, bins, both, 1, invC, nullptr, nullptr, nullptr, nullptr, nullptr,
+                     counts, tail);
+}
+
+int crbm_compare_ms(crbm_handle* h, float* ms, float* stage_ms) {
+  if (!h || !ms) return CRBM_ERR_INVALID;
+  *ms = h->compare_ms[0];
+  if (stage_ms)
+    for (int i = 0; i < 3; ++i) stage_ms[i] = h->compare_ms[i + 1];
   return CRBM_OK;
 }
 

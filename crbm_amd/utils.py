@@ -1,4 +1,4 @@
-"""Motif export and motif-site export.
+"""Motif export, motif-site export and motif-match export.
 
 secomo/utils.py:16-47 writes one file per motif through Bio.motifs.jaspar;
 this writer produces the same text layouts without Biopython.  The plotting
@@ -58,6 +58,18 @@ def saveSites(model, sites, filename, names=None, fformat="bed", name="mot"):
         chrom = names[seq] if names is not None else "seq{:d}".format(seq)
         lines.append("\t".join([chrom, str(start), str(start + M), "{}{:d}".format(name, k + 1),
                                 "{:.6g}".format(float(r["prob"])), _STRAND[int(r["strand"])]]))
+    with open(filename, "w") as f:
+        f.write("".join(line + "\n" for line in lines))
+
+
+def saveMatches(comparison, filename, evalue=10.0):
+    """Write the matches of a MotifComparison (compareMotifs) with an E-value of at most `evalue` to a tab file under a
+    header line: query, target, offset, strand (+ -), overlap, p-value, E-value, q-value; sorted by query, then p-value."""
+    lines = ["query\ttarget\toffset\tstrand\toverlap\tpvalue\tevalue\tqvalue"]
+    for r in comparison.matches(evalue=evalue):
+        lines.append("\t".join([comparison.queries[int(r["query"])], comparison.targets[int(r["target"])], str(int(r["offset"])),
+                                _STRAND[int(r["strand"])], str(int(r["overlap"]))] +
+                               ["{:.6g}".format(float(r[f])) for f in ("pvalue", "evalue", "qvalue")]))
     with open(filename, "w") as f:
         f.write("".join(line + "\n" for line in lines))
 

@@ -587,6 +587,51 @@ int crbm_score_distribution(crbm_handle* h, const int32_t* q, int32_t R, int32_t
                             const double* init, int64_t G, double* pmf);
 int crbm_null_ms(crbm_handle* h, float* ms);
 
+/* ---- Motif comparison: every placement of every query motif on every target motif, with exact p-values --------------
+ * Model-independent, like the analytic null above: the handle of any model lends its device, its main stream and its
+ * error string.  Every pointer is host memory; the call is complete when it returns.  (Additive: the ABI version stays.)
+ *
+ * A motif is w columns of four uint16 (A, C, G, T): x = clip(floor(p * 4096 + 0.5), 0, 4096).  qcols (qstart[K], 4) holds
+ * the columns of the K queries, query k in the rows [qstart[k], qstart[k + 1]); tcols and tstart the N targets.  The
+ * reverse complement of a motif has its columns reversed and its letters swapped A <-> T, C <-> G.  Two columns score
+ *   D = sum_a (x_a - y_a)^2;   sim = 2^25 - min(D, 2^25);   bin = (sim * (bins - 1) + 2^24) >> 25   in [0, bins),
+ * exact integers.  The pool is every target column (both != 0: and every column of every reverse complement), C columns.
+ * For a query of width m:
+ *   count[i][y]  the pool columns whose bin against query column i is y;   col[i][y] = (double)count[i][y] * invC
+ *   pmf_{i,0} = [1];   pmf_{i,l}[x] = sum_{y = 0 .. bins - 1} pmf_{i,l-1}[x - y] * col[i+l-1][y],   x < G_l = l (bins - 1) + 1
+ *   tail_{i,l}[G_l] = 0;   tail_{i,l}[x] = tail_{i,l}[x + 1] + pmf_{i,l}[x]
+ * All float64, a product and an add rounded separately; the terms of a cell are added in ascending y from 0.0 (terms
+ * outside the support are not added), the tails sequentially with x descending.  invC = 1.0 / C is the caller's.
+ * Placement of a target of width n at offset o = -(n - 1) .. m - 1 (target column j under query column j + o):
+ * i0 = max(0, o), j0 = max(0, -o), l = min(m - i0, n - j0); it is evaluated when l >= min(min_overlap, m, n), scores
+ * S = sum_{t < l} bin(query column i0 + t, target column j0 + t) and has the p-value tail_{i0,l}[S].  Strand -1 places the
+ * target's reverse complement by the same rule (both != 0 only).
+ *
+ * crbm_motif_compare: (K, N) outputs.  p_min: the smallest placement p-value of the pair; offset, strand (+1 / -1) and
+ * overlap (l): that placement, ties on bit-equal p going to strand +1, then to the smaller offset; n_off: the
+ * placements evaluated.  Everything is an integer up to the counts and one summation order from there: the same inputs
+ * give the same bits whatever the launch geometry, the targets per block (CRBM_COMPARE_TILE, default 32, at most 64) and
+ * the grouping of queries -- the tail tables of a group, sum_l (m - l + 1) (G_l + 1) * 8 bytes per query, and its 21
+ * bytes per output pair stay within CRBM_COMPARE_BYTES (default 1 GiB).
+ *
+ * crbm_motif_compare_null: one query of width m.  counts (m, bins) uint32, and tail: the tables packed by start i
+ * ascending, then l = 1 .. m - i ascending, G_l + 1 doubles each.
+ *
+ * CRBM_ERR_INVALID, before anything is launched: a null pointer; K or N < 1; a width outside [1, 64]; a start array
+ * that does not begin at 0 or does not ascend; an entry above 4096; bins outside [2, 256]; min_overlap < 1; a pool
+ * beyond 2^31 - 1 columns; invC outside (0, 1]; a single query whose tables and output row do not fit
+ * CRBM_COMPARE_BYTES.  The outputs are not written then, and the handle stays usable.
+ *
+ * crbm_compare_ms: device time (HIP events around the kernels of every group, summed) of the handle's last
+ * crbm_motif_compare or crbm_motif_compare_null call; stage_ms, where not null, receives three floats: counts, null,
+ * placements. */
+int crbm_motif_compare(crbm_handle* h, const uint16_t* qcols, const int32_t* qstart, int32_t K, const uint16_t* tcols,
+                       const int32_t* tstart, int32_t N, int32_t bins, int32_t both, int32_t min_overlap, double invC,
+                       double* p_min, int32_t* offset, int8_t* strand, int32_t* overlap, int32_t* n_off);
+int crbm_motif_compare_null(crbm_handle* h, const uint16_t* qcols, int32_t m, const uint16_t* tcols, const int32_t* tstart,
+                            int32_t N, int32_t bins, int32_t both, double invC, uint32_t* counts, double* tail);
+int crbm_compare_ms(crbm_handle* h, float* ms, float* stage_ms);
+
 #ifdef __cplusplus
 }
 #endif
